@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """Headline benchmark: agent-steps/s of the HIP step engine on rware-small-4ag, batch 16384 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          # N > 1: spawns one process per GPU itself
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   # N > 1: spawns one process per GPU itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   # or under a launcher
+
+A plain run sets up, runs W warm-up and K timed steps, writes the last timed step's outputs (--dump-outputs) and prints
+the line: value, ms_per_step, config, roofline, ranks.  The side measurements below (sustained, soak, fused_rollout,
+roofline.store_only_*, the per-rank host-issue / graph figures, api_closed_loop, hbm_regime, two_pipelines, cpu_baseline)
+run after the timed steps only with --full.
 
 One "step" = one pass of the hot path (Warehouse.step + FLATTENED obs, rware/warehouse.py:804-946)
 over the whole env batch resident in HBM: one `rw_step_device` call, actions read from a
@@ -26,8 +31,8 @@ The printed JSON line carries
                         does not move (a work rate in that unit; it may exceed 1).  `regime`: whether a step's bytes fit the
                         256 MiB Infinity Cache ("infinity-cache") or not ("hbm")
   (--submit graph: the same per-step launches replayed from a HIP graph — for rocprofv3 traces, see profiles/tools/sweep.sh)
-  cpu_baseline (N = 1)  the reference's pure-Python step on the host cores when /root/reference exists, else the C port
-                        of it, 1 process and one per core, with the core count and CPU model
+  cpu_baseline (N = 1)  the reference's pure-Python step on the host cores when a reference tree is found (oracle/ref_runner.py),
+                        else the C port of it, 1 process and one per core, with the core count and CPU model
 """
 import argparse
 import hashlib
@@ -66,6 +71,32 @@ def roofline_fields(a_bytes, e_bytes, traffic, k_ms):
         "algorithmic_bytes_per_launch": a_bytes, "engine_bytes_per_launch": e_bytes,
         "peak": HBM_PEAK_GBPS, "peak_measured": HBM_MEASURED_GBPS,
     }
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all (.npy headers included)
+
+
+def dump_outputs(eng, out_dir, features=False, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what a caller of the timed path receives after its last step — obs, rewards, terminated, truncated
+    (and the IMAGE_DICT features) — as out_dir/<name>.npy in float32.  Past `budget` bytes, the same fixed, seeded sample of
+    envs from every array, in env order, with the env indices beside them (sample_env_index.npy).  Returns the names written."""
+    obs, rew, term, feat = eng.read_outputs(want_features=features)
+    arrays = {"obs": obs, "rewards": rew, "terminated": term, "truncated": eng.read("truncated")}
+    if features:
+        arrays["features"] = feat
+    B = obs.shape[0]
+    per_env = sum(a[0].size for a in arrays.values()) * 4
+    if per_env * B > budget:
+        keep = max(1, (budget - 4096) // (per_env + 8))  # (+ 8: the float64 index of each sampled env; 4096: the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+    return sorted(arrays)
+
+
 def floor_fraction(floor_ms, k_ms):
     """store-only kernel time / step kernel time.  A kernel that only writes the observations cannot take longer than the one that also
     computes them: a ratio above 1 means the two measurements were disturbed differently (ranks sharing one device in the rehearsal tests, a
@@ -476,6 +507,15 @@ def main():
                          "auto = native at EVERY N (the N = 1 number and the N > 1 numbers of a scaling curve then take the same "
                          "path); every rank also reports, beside it, the same launches replayed from a HIP graph and the host time "
                          "per issued launch (`ranks[i].graph_ms_per_step`, `.host_issue_us_per_step`) — SURVEY.md §8(e)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement after the timed steps: sustained, soak, fused rollout, store-only floor, "
+                         "host-issue / HIP-graph modes, closed-loop API, HBM regime, two pipelines, CPU baseline (each can be "
+                         "switched off with its --no-* flag).  Without it a run sets up, warms up, times --steps steps, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (obs, rewards, terminated, truncated; "
+                         "features for IMAGE_DICT) as DIR/<name>.npy in float32, rank 0's shard; a fixed, seeded sample of envs "
+                         f"(DIR/sample_env_index.npy) when the arrays exceed {DUMP_BUDGET_BYTES // 10**6} MB")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fused-extra", action="store_true", help="skip the extra fused-rollout measurement (profiling runs)")
     ap.add_argument("--no-sustained", action="store_true", help="skip the fixed 2000-step sustained leg (profiling runs)")
@@ -484,6 +524,11 @@ def main():
     ap.add_argument("--no-api-loop", action="store_true", help="skip the Python closed-loop API leg")
     ap.add_argument("--no-submit-modes", action="store_true", help="skip the per-rank host-issue / HIP-graph side measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: only what the headline figure needs
+        args.no_cpu_baseline = args.no_fused_extra = args.no_sustained = args.no_soak = True
+        args.no_hbm_regime = args.no_api_loop = args.no_submit_modes = True
 
     if args.submit == "auto":
         args.submit = "native"  # (the same submission path at every N; the graph path is measured beside it, per rank)
@@ -611,6 +656,8 @@ def main():
     elapsed, kernel_ms = timed(args.steps, t_next)
     t_next += args.steps
     eng.sync()  # surfaces a sticky device-side error (invalid action) outside the timed region
+    if args.dump_outputs and rank == 0:  # before any side measurement steps the engine further
+        dump_outputs(eng, args.dump_outputs, features=args.observation_type == 3)
 
     sus = None
     if not args.no_sustained:
@@ -645,7 +692,7 @@ def main():
     # The practical floor beside the 8 TB/s one: a kernel that only WRITES this step's observations (same geometry, same store
     # instruction), launched back to back like the step kernel (rw_debug_store_floor)
     try:
-        floor_ms = eng.debug_store_floor(2000 if B * N <= 1 << 18 else 200) if args.many == 0 else None
+        floor_ms = eng.debug_store_floor(2000 if B * N <= 1 << 18 else 200) if (args.many == 0 and args.full) else None
     except Exception:  # noqa: BLE001  (a side measurement)
         floor_ms = None
     # Every rank, at every N (N = 1 included): what a launch costs this rank's host thread, and the same launches replayed from a HIP

@@ -15,8 +15,10 @@ python -m pytest tests -m gpu -q --tb=short -rs --durations=10 2>&1 | tail -80 >
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3 | tee gpurun_out/${TAG}_smoke.txt
 bash profiles/tools/sweep.sh $TAG 2>&1 | tail -15
 cp gpurun_out/pmc_traffic.json profiles/pmc_traffic.json
-python bench.py > gpurun_out/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.err
-python bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_k20.json 2> /dev/null
+# the bench lines with every side measurement (--full), written to $BENCH_OUT (default: profiles/, where they are kept)
+BENCH_OUT=${BENCH_OUT:-profiles}
+python bench.py --full > "$BENCH_OUT/${TAG}_bench_default.json" 2> "$BENCH_OUT/${TAG}_bench_default.err"
+python bench.py --full --steps 20 --warmup 5 > "$BENCH_OUT/${TAG}_bench_k20.json" 2> /dev/null
 python profiles/tools/timeline_probe.py 2>&1 | grep -v amdgpu.ids > gpurun_out/${TAG}_timeline.txt
 python profiles/tools/timeline_probe.py rware-small-4ag-v1 262144 2>&1 | grep -v amdgpu.ids > gpurun_out/${TAG}_timeline_B262144.txt
 TL_OBS_TYPE=2 python profiles/tools/timeline_probe.py 2>&1 | grep -v amdgpu.ids > gpurun_out/${TAG}_timeline_image.txt
@@ -45,7 +47,7 @@ bash profiles/tools/unprofiled.sh $TAG > gpurun_out/${TAG}_unprofiled.txt
 cat gpurun_out/${TAG}_unprofiled.txt
 python - <<PY
 import json
-for f in ("gpurun_out/${TAG}_bench_default.json", "gpurun_out/${TAG}_bench_k20.json"):
+for f in ("$BENCH_OUT/${TAG}_bench_default.json", "$BENCH_OUT/${TAG}_bench_k20.json"):
     d = json.loads(open(f).read().strip().splitlines()[-1])
     print(f, "G=%.3f" % (d["value"] / 1e9), "us/step=%.3f" % (d["ms_per_step"] * 1e3), "sustained=%.3f" % (d["sustained"]["ms_per_step"] * 1e3),
           "traffic=", d["roofline"]["traffic"], "frac=%.3f (%s, %s)" % (d["roofline"]["frac"], d["roofline"]["basis"], d["roofline"]["regime"]), "frac_algorithmic=%.3f" % d["roofline"]["frac_algorithmic"])

@@ -3,7 +3,7 @@
 TAG=${1:-r02}
 OUT=gpurun_out/${TAG}_unprofiled.jsonl
 : > $OUT
-COMMON="--no-cpu-baseline --no-hbm-regime --no-api-loop --no-fused-extra --no-submit-modes --no-soak"
+COMMON="--full --no-cpu-baseline --no-hbm-regime --no-api-loop --no-fused-extra --no-submit-modes --no-soak"
 run() { name=$1; tape=$2; shift 2; RWARE_BENCH_TAPE_STEPS=$tape python bench.py $COMMON "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); d['sweep_config']='$name'; print(json.dumps(d))" >> $OUT; }
 run headline_small4_B16384 256 --steps 6000 --warmup 200
 run cfg2_tiny2_B4096 256 --env-id rware-tiny-2ag-v1 --batch 4096 --steps 6000 --warmup 200

@@ -1,6 +1,7 @@
 """Adapters that let the shared replay harness (golden_util.replay) drive the product's
 WarehouseVecEnv — either through the real gfx950 library (GPU tests) or through the
 host-thread emulation build of the same sources (tests/emu, CPU-only container)."""
+import fcntl
 import os
 import subprocess
 
@@ -17,7 +18,11 @@ def build_emu() -> str:
     other = os.environ.get("RWARE_EMU_LIB")
     if other:
         return other
-    subprocess.check_call(["make", "-s", "-j8", "-C", EMU_DIR], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    # one make at a time: pytest-xdist workers all get here at collection, and on a fresh checkout concurrent makes would
+    # write the same objects and re-link the library under a worker that has already loaded it
+    with open(os.path.join(EMU_DIR, "Makefile")) as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        subprocess.check_call(["make", "-s", "-j8", "-C", EMU_DIR], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return EMU_LIB
 
 

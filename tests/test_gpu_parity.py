@@ -589,7 +589,7 @@ def test_bench_two_ranks_self_spawned():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["RWARE_BENCH_SHARE_GPU"] = "1"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "200", "--warmup", "20", "--batch", "4096", "--no-soak"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "200", "--warmup", "20", "--batch", "4096", "--full", "--no-soak"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     _check_bench_line(out, 2, 200, 20, 4096)
 
@@ -625,7 +625,7 @@ def test_bench_two_ranks_through_torchrun():
     env = dict(os.environ, RWARE_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29731", os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "200", "--warmup", "20", "--batch", "4096", "--no-soak"]
+           "--gpus", "2", "--steps", "200", "--warmup", "20", "--batch", "4096", "--full", "--no-soak"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     _check_bench_line(out, 2, 200, 20, 4096)
 
@@ -740,7 +740,7 @@ def test_bench_eight_ranks_report_placement_and_per_rank_times():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["RWARE_BENCH_SHARE_GPU"] = "1"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "300", "--warmup", "20", "--batch", "2048", "--no-soak"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "300", "--warmup", "20", "--batch", "2048", "--full", "--no-soak"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     d = _check_bench_line(out, 8, 300, 20, 2048)
     ranks = d["ranks"]
@@ -754,7 +754,7 @@ def test_bench_eight_ranks_report_placement_and_per_rank_times():
 
 
 def test_bench_driver_invocation_carries_every_leg():
-    """The driver's own N = 1 call, `bench.py --steps 20 --warmup 5`: ONE line with roofline, sustained, the HBM-regime leg,
+    """The driver's N = 1 call with every side measurement, `bench.py --steps 20 --warmup 5 --full`: ONE line with roofline, sustained, the HBM-regime leg,
     the closed-loop API leg, and the CPU baseline north_star names — the reference's pure-Python step (staged, unmodified,
     under the git-ignored oracle/_ref) timed on THIS box's cores, the C port beside it."""
     import json
@@ -762,7 +762,7 @@ def test_bench_driver_invocation_carries_every_leg():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5"], env=env, cwd=root,
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--full"], env=env, cwd=root,
                          capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -783,6 +783,45 @@ def test_bench_driver_invocation_carries_every_leg():
     assert c["cores"] >= 1 and c["port"]["aggregate"] > 0
     if os.path.isfile(os.path.join(root, "oracle", "_ref", "rware", "warehouse.py")):
         assert c["kind"] == "reference" and c["value"] > 0 and "oracle/_ref" in c["reference_root"], c
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """A plain `bench.py` run (no --full): the headline keys and no side measurement; --dump-outputs writes the outputs of the
+    last timed step in float32, the same from run to run, and equal to the oracle after the same W + K steps of the same tape."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    B, K, W = 4096, 300, 20
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / f"run{run}")
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(K), "--warmup", str(W), "--batch", str(B),
+                              "--dump-outputs", d], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == K and line["warmup"] == W and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+        assert line["unit"] == "agent-steps/s" and line["dtype"] == "int32" and line["metric"].startswith("agent-steps/sec")
+        assert abs(line["value"] - B * 4 * K / (line["ms_per_step"] * 1e-3 * K)) / line["value"] < 1e-6
+        for leg in ("sustained", "soak", "fused_rollout", "api_closed_loop", "hbm_regime", "two_pipelines", "cpu_baseline"):
+            assert leg not in line, leg
+        assert line["roofline"]["store_only_kernel_ms_per_launch"] is None and "graph_ms_per_step" not in line["ranks"][0]
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    assert sorted(dumps[0]) == ["obs", "rewards", "terminated", "truncated"]
+    for k, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.array_equal(a, dumps[1][k]), k
+    # the oracle over the bench's own inputs: seeds 0 .. B-1, actions row t % 256 of default_rng(12345)'s tape
+    kw = rware_amd.env_kwargs("rware-small-4ag-v1")
+    orc = OracleVecEnv(B, **dict(kw, reward_type=kw["reward_type"].value))
+    orc.reset(seed=0)
+    tape = np.random.default_rng(12345).integers(0, 5, size=(256, B, 4, 1), dtype=np.int32)[..., 0]
+    for t in range(W + K):
+        obs, rew, done = orc.step_autoreset(tape[t % 256], "next_step")
+    assert np.array_equal(dumps[0]["obs"], obs) and np.array_equal(dumps[0]["rewards"], rew)
+    assert np.array_equal(dumps[0]["terminated"], done.astype(np.float32)) and not dumps[0]["truncated"].any()
 
 
 PAPER_GRID = [f"rware-{size}-{n}ag{diff}-v1" for size in ("tiny", "small", "medium") for n in (2, 4, 6, 8) for diff in ("-easy", "", "-hard")]

@@ -163,6 +163,40 @@ def test_kernel_sources_hash_ignores_comments_and_layout():
     assert len(bench.kernel_sources_sha()) == 16
 
 
+@pytest.mark.parametrize("B", [512, 262144])
+def test_bench_dump_outputs_fits_its_budget_with_a_fixed_sample(tmp_path, B):
+    """bench.dump_outputs (--dump-outputs): every returned array as float32 .npy; past the budget the same seeded env sample from
+    every array, in env order, with its indices, and the whole dump under the budget."""
+    import bench
+
+    class FakeEngine:   # what bench.py reads from the engine after its last timed step
+        def __init__(self):
+            rng = np.random.default_rng(B)
+            self.obs = rng.random((B, 4, 71), dtype=np.float32)
+            self.rew = rng.random((B, 4), dtype=np.float32)
+            self.term = (rng.random(B) < 0.1).astype(np.uint8)
+
+        def read_outputs(self, want_features=False):
+            return self.obs, self.rew, self.term, None
+
+        def read(self, name):
+            assert name == "truncated"
+            return np.zeros(B, np.uint8)
+
+    eng, budget = FakeEngine(), 4 << 20
+    names = bench.dump_outputs(eng, str(tmp_path), budget=budget)
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in names}
+    assert sum(os.path.getsize(tmp_path / f"{n}.npy") for n in names) <= budget
+    assert all(a.dtype == (np.float64 if n == "sample_env_index" else np.float32) for n, a in got.items())
+    idx = got["sample_env_index"].astype(np.int64) if "sample_env_index" in got else np.arange(B)
+    assert ("sample_env_index" in got) == (B * (4 * 71 + 4 + 2) * 4 > budget) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got["obs"], eng.obs[idx]) and np.array_equal(got["rewards"], eng.rew[idx])
+    assert np.array_equal(got["terminated"], eng.term[idx].astype(np.float32)) and not got["truncated"].any()
+    again = tmp_path / "again"
+    bench.dump_outputs(eng, str(again), budget=budget)
+    assert all(np.array_equal(got[n], np.load(again / f"{n}.npy")) for n in names)
+
+
 def test_pmc_traffic_record_belongs_to_these_kernel_sources():
     """profiles/pmc_traffic.json — the rocprofv3 FETCH_SIZE / WRITE_SIZE passes behind `roofline.traffic` — must have been measured on
     the kernel sources in this tree, or bench.py reports `traffic: null` (`basis: "engine-bytes"`).  A kernel edit after the evidence
