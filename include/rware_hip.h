@@ -115,12 +115,12 @@ enum rw_stream_flags {
      * to the agent phases), in every launch form: rw_step*, fused rollouts, tapes, HIP graphs, rw_multi. */
     RW_STATS_ON = 128,
     /* Wavefront priority (rw_info.wave_priority): the launches run the dependent chain in front of their first observation store at raised
-     * priority by rw_create's measured rule (on, except the per-step launches of 13 .. 16 agents at sensor_range 1 and steps of 200 MB of
-     * observations and more).  RW_PRIO_OFF: never — what rware_amd.make_pipelines asks for when a sub-batch has 8192 envs or fewer: with TWO
-     * launches in flight the raised chain of one takes the issue slots of the other's store phase, which is what fills the gap (two
-     * pipelines of 8192 envs, per step of the whole batch: small-8ag 7.9 us without against 9.1 with, small-10ag 10.7 / 11.9, medium-13ag
-     * 13.4 / 15.4; profiles/r06_pipelines_prio.txt).  RW_PRIO_ON: always (per-step launches and fused rollouts alike).  A scheduling
-     * hint either way: same results.  (A/B runs: RWARE_PRIO=0|1, RWARE_PRIO_ROLLOUT=0|1 with RWARE_HOOKS=1 move the default only.) */
+     * priority by rw_create's measured rule (on, except the per-step launches of 13 .. 16 agents at sensor_range 1 on 8-env workgroups
+     * beyond half a round of workgroups, and steps of 200 MB of observations and more).  RW_PRIO_OFF: never — what rware_amd.make_pipelines
+     * asks for when a sub-batch has 8192 envs or fewer: with TWO launches in flight the raised chain of one takes the issue slots of the
+     * other's store phase, which is what fills the gap (two pipelines of 8192 envs, per step of the whole batch: small-8ag 7.9 us without
+     * against 9.1 with, small-10ag 10.7 / 11.9, medium-13ag 13.4 / 15.4; profiles/r06_pipelines_prio.txt).  RW_PRIO_ON: always (per-step
+     * launches and fused rollouts alike).  A scheduling hint either way: same results.  (A/B runs: RWARE_PRIO=0|1, RWARE_PRIO_ROLLOUT=0|1 with RWARE_HOOKS=1 move the default only.) */
     RW_PRIO_OFF = 256,
     RW_PRIO_ON = 512
 };
@@ -329,9 +329,10 @@ typedef struct rw_info {
                              the barrier behind the agent phases, so that the dependent chain in front of the first observation store is
                              not queued behind the neighbours' store phase on the same CU; bit 1: the fused rollouts do (every step of the
                              launch).  rw_create's measured rule: on while a step's observations stay under 200 MB (past that nothing moves),
-                             the per-step launches of 13 .. 16 agents at sensor_range 1 excepted (A/B runs: RWARE_PRIO=0|1,
-                             RWARE_PRIO_ROLLOUT=0|1 with RWARE_HOOKS=1).  A scheduling hint, never a different result.  (The slot was
-                             `state_layout`, 0 since round 3.) */
+                             except for the per-step launches of 13 .. 16 agents at sensor_range 1 on 8-env workgroups beyond half a round
+                             of workgroups (on their 4-env workgroups, and up to half a round of 8-env ones, it is on) (A/B runs:
+                             RWARE_PRIO=0|1, RWARE_PRIO_ROLLOUT=0|1 with RWARE_HOOKS=1).  A scheduling hint, never a different result.
+                             (The slot was `state_layout`, 0 since round 3.) */
     int32_t build_kind;   /* which build of the step kernel runs: 0 generic (every shape at run time), 1 exact-shape, 2 agent-count-
                              static (shapes + agent count folded in, request-queue length at run time), 3 size-static (grid folded in,
                              agent count and queue length at run time).  (Occupies what was alignment padding: same struct size.) */
@@ -347,12 +348,13 @@ typedef struct rw_info {
                                   terminated (+ messages r/w, IMAGE_DICT features).  The PMC traffic of a step is checked against
                                   it; bench.py prices `frac_engine` on it (<= 1 by construction)                               */
     int32_t stagger_ticks;     /* > 0: the k-th of the first eight workgroups a CU receives starts k * stagger_ticks * 10 ns late, so that
-                                  the workgroups of a CU do not run their load / agent / store phases in lock-step.  rw_create's measured rule:
-                                  13 .. 16 agents at sensor_range 1 — 550 ns at one round and from four rounds on; launches that do NOT run at
-                                  raised wavefront priority (wave_priority bit 0 clear: steps of >= 200 MB of observations) — <= 12 agents 250 ns
-                                  from two rounds of workgroups on, 13 .. 16 agents at sensor_range 2 400 ns up to two rounds; else 0: with the
-                                  priority the delay is only a delay (A/B runs: RWARE_STAGGER_TICKS=n with RWARE_HOOKS=1; 0 = off).  A delay,
-                                  never a different result */
+                                  the workgroups of a CU do not run their load / agent / store phases in lock-step.  rw_create's measured rule,
+                                  in rounds of the per-step launches' workgroups: 13 .. 16 agents at sensor_range 1 on 8-env workgroups —
+                                  550 ns from half a round to one round and from four rounds on; launches that do NOT run at raised wavefront
+                                  priority (wave_priority bit 0 clear: steps of >= 200 MB of observations) — <= 12 agents 250 ns from two
+                                  rounds on, 13 .. 16 agents at sensor_range 2 400 ns up to two rounds; else 0: with the priority the delay is
+                                  only a delay (A/B runs: RWARE_STAGGER_TICKS=n with RWARE_HOOKS=1; 0 = off).  The fused rollouts carry the
+                                  same value.  A delay, never a different result */
     int32_t pipe_envs_per_workgroup; /* != 0: rw_step* launches run the chunk-pipelined persistent build with chunks of this many envs ... */
     int32_t pipe_workgroups;         /* ... on this many persistent workgroups (rw_stream_flags RW_PIPE_ON / RW_PIPE_OFF)              */
     int32_t stats;                   /* 1: RW_STATS_ON — RW_BUF_STAT_* are kept (was `reserved[1]`: same struct size)                 */

@@ -992,6 +992,18 @@ def test_wave_priority_is_a_create_time_rule_and_does_not_change_results(monkeyp
     on.close(); off.close()
 
 
+def test_lds_limit_refuses_the_geometry_and_names_the_footprint():
+    """rw_create refuses a workgroup geometry whose LDS footprint (the larger of the per-step and the fused-rollout plans') exceeds
+    160 KiB, and the message names the footprint it tested."""
+    kw = rware_amd.env_kwargs("rware-tiny-1ag-v1")
+    env = rware_amd.WarehouseVecEnv(256, library=LIB, envs_per_workgroup=256, **kw)     # (one agent: E * N * N stays small)
+    assert env.engines[0].info.lds_bytes <= 160 * 1024
+    env.close()
+    with pytest.raises(rware_amd._capi.EngineError, match=r"LDS footprint \d+ B exceeds 160 KiB; lower envs_per_workgroup") as ei:
+        rware_amd.WarehouseVecEnv(512, library=LIB, envs_per_workgroup=512, **kw)
+    assert int(str(ei.value).split("LDS footprint ")[1].split()[0]) > 160 * 1024
+
+
 def test_13_to_16_agents_step_on_4_env_workgroups_and_roll_out_on_8(monkeypatch):
     """Round 6: 13 .. 16 agents at sensor_range 1 — the per-step launches run on 4-env workgroups (one agent wavefront each) at raised
     wavefront priority below one full round of 8-env workgroups and between one and four rounds, on the start-staggered 8-env build at
