@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-#define RW_ABI_VERSION 3
+/* 4 (since 3): RW_OBS_PACKED in rw_stream_flags, RW_BUF_OBS_PACKED (RW_BUF_KIND_COUNT 22 -> 23), rw_info.obs_packed appended (the struct
+ * grows by 8 bytes), rw_unpack_obs, a 16th element (`packed`) in rw_jit_probe's shape.  Everything else is unchanged. */
+#define RW_ABI_VERSION 4
 
 typedef struct rw_engine rw_engine;
 
@@ -112,7 +114,10 @@ enum rw_stream_flags {
     /* Event counters (SURVEY.md §5 "metrics"): with RW_STATS_ON the engine keeps two running totals per env in RW_BUF_STAT_DELIVERIES and
      * RW_BUF_STAT_FAILED_MOVES (below) — off by default, and the reference's `info` stays {} either way (rware/warehouse.py:746-747).
      * Counted by the service wavefront beside the observation stores (re-derived from what the state write-back holds; nothing is added
-     * to the agent phases), in every launch form: rw_step*, fused rollouts, tapes, HIP graphs, rw_multi. */
+     * to the agent phases), in every launch form: rw_step*, fused rollouts, tapes, HIP graphs, rw_multi.
+     * Which kernels run with it: the ahead-of-time exact-shape builds do not carry the counting code, so below 4096 envs, with RW_JIT_OFF
+     * or without hipRTC the generic kernel runs (rw_info.build_kind == 0); from 4096 envs on rw_create compiles an exact-shape build with
+     * the counters through hipRTC at construction (seconds; cached on disk as described at RW_JIT_OFF; rw_info.jit says which happened). */
     RW_STATS_ON = 128,
     /* Wavefront priority (rw_info.wave_priority): the launches run the dependent chain in front of their first observation store at raised
      * priority by rw_create's measured rule (on, except the per-step launches of 13 .. 16 agents at sensor_range 1 on 8-env workgroups
@@ -122,7 +127,25 @@ enum rw_stream_flags {
      * against 9.1 with, small-10ag 10.7 / 11.9, medium-13ag 13.4 / 15.4; profiles/r06_pipelines_prio.txt).  RW_PRIO_ON: always (per-step
      * launches and fused rollouts alike).  A scheduling hint either way: same results.  (A/B runs: RWARE_PRIO=0|1, RWARE_PRIO_ROLLOUT=0|1 with RWARE_HOOKS=1 move the default only.) */
     RW_PRIO_OFF = 256,
-    RW_PRIO_ON = 512
+    RW_PRIO_ON = 512,
+    /* Bit-packed FLATTENED observations.  Every element of a FLATTENED observation except the two coordinates is 0.0 or 1.0
+     * (rware/warehouse.py:643-673); with RW_OBS_PACKED the launches write the bits instead of 4 bytes per bit:
+     *   RW_BUF_OBS_PACKED  uint32 [B][N][PW], PW = 1 + ceil(L / 32), L = rw_info.obs_length
+     *     word 0                    x | y << 16 — the agent's cell indices as integers, whatever normalised_coordinates says
+     *     word 1 + k / 32, bit k % 32   obs[k] != 0, for 2 <= k < L; bits 0 and 1 of word 1 (the coordinate slots) and the bits from L
+     *                               upwards in the last word are 0
+     * (sensor_range 1 without messages: L = 71, PW = 4 — 16 bytes per agent instead of 284).  Unpacking — obs[0] = coord(x, W), obs[1] =
+     * coord(y, H) with coord the identity or, with normalised_coordinates, float32(float64(v) / float64(dim - 1)); obs[k] = float32(bit k)
+     * — reproduces RW_BUF_OBS bit for bit: rw_unpack_obs on the device, rware_amd.unpack_obs in Python.
+     * With the flag RW_BUF_OBS is NOT allocated (0 bytes; rw_read of it and the `obs` argument of rw_read_outputs fail with
+     * RW_ERR_UNSUPPORTED); RW_BUF_FINAL_OBS (SAME_STEP autoreset) stays float32.  rw_reset, rw_refresh_obs, snapshots' restore, the fused
+     * rollouts and captured graphs all produce packed rows.  FLATTENED only: the IMAGE types fail with RW_ERR_UNSUPPORTED (the
+     * AGENT_DIRECTION layer holds dir + 1).  Off by default; the float32 rows stay the default and the parity path.
+     * Which kernels run with it: the ahead-of-time exact-shape builds do not carry the packed rows and are never used; below 4096 envs, with
+     * RW_JIT_OFF or without hipRTC the generic kernel runs (rw_info.build_kind == 0); from 4096 envs on (or with RW_JIT_FORCE) rw_create
+     * compiles an exact-shape packed build through hipRTC at construction (seconds; cached on disk as described at RW_JIT_OFF; rw_info.jit
+     * says which happened).  RW_PIPE_ON | RW_OBS_PACKED: the classic kernel runs and rw_jit_log() says so. */
+    RW_OBS_PACKED = 1024
 };
 
 /* Device buffers (all env-major, C-contiguous).  Replaces the attributes callers read off the
@@ -172,7 +195,10 @@ enum rw_buffer_kind {
     RW_BUF_STAT_FAILED_MOVES = 21, /* int32 [B]  (agent, step) pairs whose FORWARD the step turned into NOOP: a loaded agent facing a
                                                  standing shelf (:836-846) or a mover that lost the collision resolution (:871-876).
                                                  A FORWARD into a wall is clamped to a self-target (:105-112) and is NOT one            */
-    RW_BUF_KIND_COUNT = 22
+    RW_BUF_OBS_PACKED = 22,  /* uint32  [B][N][PW] RW_OBS_PACKED only (empty otherwise; RW_BUF_OBS is empty then): the FLATTENED observation
+                                                   as bits, PW = 1 + ceil(L / 32) words per agent — the format at RW_OBS_PACKED.  Read-only
+                                                   (rw_write refuses it)                                                        */
+    RW_BUF_KIND_COUNT = 23
 };
 
 /* Mirrors the constructor of rware.warehouse.Warehouse (rware/warehouse.py:146-170).  The
@@ -246,7 +272,10 @@ int rw_step_tape_device(rw_engine *eng, const int32_t *tape_dev, int32_t tape_st
 int rw_step_tape_device_timed(rw_engine *eng, const int32_t *tape_dev, int32_t tape_steps, int32_t first, int32_t n_steps,
                               int32_t start_slot, int32_t stop_slot);
 
-/* T consecutive steps from a device-resident action tape int32 [T][B][N] in ONE kernel launch: each
+/* RW_OBS_PACKED engines: the signature stays, and a non-NULL `obs_tape` receives PACKED rows — uint32 [T][B][N][PW] — through the same
+ * pointer (rw_unpack_obs takes any row count, so one call unpacks a whole tape).  Any 4-byte-aligned tape works; one that starts on a
+ * 16-byte boundary gets 16-byte stores.
+ * T consecutive steps from a device-resident action tape int32 [T][B][N] in ONE kernel launch: each
  * workgroup keeps its env chunk in LDS across the T steps, so per step only the actions are read and
  * obs / rewards / terminated written (rollout API; open-loop by construction —
  * the tape must exist before the launch).  Results are identical to T rw_step_device calls.  If `obs_tape` /
@@ -286,8 +315,14 @@ int rw_set_stream(rw_engine *eng, void *stream);
  * the derived views on every request; this call is for graphs captured by other means. */
 int rw_mark_views_stale(rw_engine *eng);
 
-/* recompute RW_BUF_OBS from the current state (after rw_write of state buffers) */
+/* recompute RW_BUF_OBS (RW_OBS_PACKED: RW_BUF_OBS_PACKED) from the current state (after rw_write of state buffers) */
 int rw_refresh_obs(rw_engine *eng);
+/* packed rows -> float32 rows on the device (no reference counterpart): `packed_dev` uint32 [n_rows][PW], `obs_f32_dev` float32
+ * [n_rows][L], both device pointers, one row per (env, agent) — RW_BUF_OBS_PACKED itself (n_rows = B * N), a slice of it, or a
+ * [T][B][N][PW] tape of rw_step_many_device (n_rows = T * B * N).  Enqueued on the engine's stream; the shape facts (L, PW, grid size,
+ * normalised_coordinates) are the engine's.  The result equals what RW_BUF_OBS would hold, bit for bit.  Any FLATTENED engine, with or
+ * without RW_OBS_PACKED. */
+int rw_unpack_obs(rw_engine *eng, const uint32_t *packed_dev, float *obs_f32_dev, int64_t n_rows);
 
 /* wait for everything enqueued; returns RW_ERR_INVALID_ACTION if any step since the last
  * rw_sync saw an out-of-range action (that action was executed as NOOP), else RW_OK */
@@ -358,15 +393,18 @@ typedef struct rw_info {
     int32_t pipe_envs_per_workgroup; /* != 0: rw_step* launches run the chunk-pipelined persistent build with chunks of this many envs ... */
     int32_t pipe_workgroups;         /* ... on this many persistent workgroups (rw_stream_flags RW_PIPE_ON / RW_PIPE_OFF)              */
     int32_t stats;                   /* 1: RW_STATS_ON — RW_BUF_STAT_* are kept (was `reserved[1]`: same struct size)                 */
+    int32_t obs_packed;              /* 1: RW_OBS_PACKED — the launches write RW_BUF_OBS_PACKED, RW_BUF_OBS is empty; engine_bytes_per_env_step
+                                        prices the packed row (appended with ABI 4)                                                  */
 } rw_info;
 int rw_get_info(const rw_engine *eng, rw_info *out);
 /* what the run-time specialisation did for this engine: cache file / compile time, or why it is not in use ("" if not tried) */
 const char *rw_jit_log(const rw_engine *eng);
 /* the compile half of the run-time specialisation, without a device (build checks, cache warm-up on a login node): `shape` =
  * {sensor_range, H, W, N, Q, S, envs per workgroup, 256, msg_bits, wide shelf ids, observation kind (0 FLATTENED, 1 IMAGE,
- * 2 FLATTENED + messages), baked image layers, packed layer list, image_directional (-1 for FLATTENED), non-temporal stores};
+ * 2 FLATTENED + messages), baked image layers, packed layer list, image_directional (-1 for FLATTENED), non-temporal stores,
+ * packed observation rows (1: the build of an RW_OBS_PACKED engine)};
  * returns the size of the gfx code object (compiled or found in the disk cache), -1 on failure (`log` says why). */
-int64_t rw_jit_probe(const int32_t shape[15], const char *arch, char *log, size_t log_len);
+int64_t rw_jit_probe(const int32_t shape[16], const char *arch, char *log, size_t log_len);
 
 /* On-device self-test (no engine needed; no reference counterpart — the reference is CPU Python): runs, on HIP device `device_id`,
  * the two toolchain / hardware facts the step kernels are written around — cross-lane exchange results compared as values in

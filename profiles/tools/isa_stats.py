@@ -2,20 +2,25 @@
 """Per-kernel ISA statistics of the exact-shape builds: compiles rware_static.hip for the given table groups to assembly
 (device only) and prints, per rw::rware_step_kernel instantiation, the instruction count, VGPRs, SGPRs, scratch and LDS.
 Usage: isa_stats.py OUTDIR [group ...]   (default groups: 0).  Used to check that a refactor leaves the BASELINE builds'
-instruction streams alone: diff two outputs."""
+instruction streams alone: diff two outputs.
+RWARE_ISA_CSRC=<dir>: compile that csrc directory instead of this tree's (a `git worktree` of another commit);
+RWARE_ISA_JSON=<file>: also write {"hipcc": <hipcc --version>, "kernels": {"g<group> <instantiation>": {inst, ophash, vgpr, sgpr, lds,
+scratch}}} — what tests/golden/isa/static_parent.json holds (tests/test_packed_obs.py compares the tree's builds against it)."""
+import json
 import os
 import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-CSRC = os.path.join(ROOT, "robotic-warehouse_amd", "csrc")
+CSRC = os.environ.get("RWARE_ISA_CSRC") or os.path.join(ROOT, "robotic-warehouse_amd", "csrc")
 
 
 def main():
     out = sys.argv[1]
     groups = [int(g) for g in sys.argv[2:]] or [0]
     os.makedirs(out, exist_ok=True)
+    record = {}
     procs = []
     for g in groups:
         s = os.path.join(out, f"static_g{g}.s")
@@ -41,7 +46,15 @@ def main():
                     if m:
                         return int(m.group(1))
                 return -1
-            print(f"g{g} {name}: inst {n_inst} vgpr {meta('NumVgprs')} sgpr {meta('NumSgprs')} scratch {meta('ScratchSize')} occ {meta('Occupancy')} ophash {oph}")
+            record[f"g{g} {name}"] = {"inst": n_inst, "ophash": oph, "vgpr": meta("NumVgprs"), "sgpr": meta("TotalNumSgprs"),
+                                      "lds": meta("LDSByteSize"), "scratch": meta("ScratchSize")}
+            print(f"g{g} {name}: inst {n_inst} vgpr {meta('NumVgprs')} sgpr {meta('NumSgprs')} total_sgpr {meta('TotalNumSgprs')} scratch {meta('ScratchSize')} occ {meta('Occupancy')} ophash {oph}")
+    if os.environ.get("RWARE_ISA_JSON"):
+        ver = subprocess.run(["/opt/rocm/bin/hipcc", "--version"], capture_output=True, text=True).stdout
+        ver = "\n".join(l for l in ver.splitlines() if "version" in l)  # (the version lines only: no install paths)
+        with open(os.environ["RWARE_ISA_JSON"], "w") as f:
+            json.dump({"hipcc": ver, "groups": groups, "kernels": record}, f, indent=1, sort_keys=True)
+            f.write("\n")
 
 
 if __name__ == "__main__":

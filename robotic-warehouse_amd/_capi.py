@@ -13,7 +13,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIBRARY = os.path.join(_HERE, "csrc", "librware_hip.so")
 
-RW_ABI_VERSION = 3
+RW_ABI_VERSION = 4
 RW_OK, RW_ERR_INVALID_ARG, RW_ERR_INVALID_ACTION, RW_ERR_HIP, RW_ERR_UNSUPPORTED, RW_ERR_NO_DEVICE, RW_ERR_INDEX, RW_ERR_SELFTEST = 0, -1, -2, -3, -4, -5, -6, -7
 
 BUF = {
@@ -21,10 +21,12 @@ BUF = {
     "agent_dir": 7, "agent_carry": 8, "agent_delivered": 9, "queue": 10, "steps": 11, "inactive": 12,
     "rng": 13, "need_reset": 14, "actions": 15, "features": 16, "agent_msg": 17, "final_obs": 18, "final_features": 19,
     "stat_deliveries": 20, "stat_failed_moves": 21,  # RW_STATS_ON only (empty otherwise)
+    "obs_packed": 22,  # RW_OBS_PACKED only (empty otherwise; "obs" is empty then)
 }
 BUF_DTYPE = {
     "obs": np.float32, "rewards": np.float32, "terminated": np.uint8, "truncated": np.uint8,
     "rng": np.uint64, "need_reset": np.uint8, "features": np.float32, "final_obs": np.float32, "final_features": np.float32,
+    "obs_packed": np.uint32,
 }
 
 RW_STREAM_USE_GIVEN = 1  # rw_stream_flags: `stream` is taken literally, NULL == the device's default stream
@@ -32,6 +34,7 @@ RW_OBS_STORES_CACHED, RW_OBS_STORES_STREAM = 2, 4  # rw_stream_flags: keep the o
 RW_JIT_OFF, RW_JIT_FORCE = 8, 16  # rw_stream_flags: run-time specialisation (hipRTC) never / always; default: shapes without an exact build, B >= 4096
 RW_PIPE_OFF, RW_PIPE_ON = 32, 64  # rw_stream_flags: the chunk-pipelined persistent per-step kernel never / wherever a build exists; default: the engine's measured rule
 RW_PRIO_OFF, RW_PRIO_ON = 256, 512  # rw_stream_flags: raised wavefront priority on the chain in front of the first store never / always; default: the engine's measured rule
+RW_OBS_PACKED = 1024  # rw_stream_flags: bit-packed FLATTENED observations — uint32 (B, N, PW) in "obs_packed", no float32 "obs" buffer
 RW_STATS_ON = 128  # rw_stream_flags: keep the per-env event counters RW_BUF_STAT_DELIVERIES / _FAILED_MOVES (off by default)
 
 AUTORESET = {"disabled": 0, None: 0, "next_step": 1, "same_step": 2}
@@ -55,12 +58,12 @@ class RwInfo(C.Structure):
         ("algorithmic_bytes_per_env_step", C.c_int64),
         ("device_name", C.c_char * 128), ("arch_name", C.c_char * 64), ("obs_stores_stream", C.c_int32), ("jit", C.c_int32),
         ("engine_bytes_per_env_step", C.c_int64), ("stagger_ticks", C.c_int32), ("pipe_envs_per_workgroup", C.c_int32),
-        ("pipe_workgroups", C.c_int32), ("stats", C.c_int32)]
+        ("pipe_workgroups", C.c_int32), ("stats", C.c_int32), ("obs_packed", C.c_int32)]
 
 
 EXPORTS = (
     "rw_create", "rw_destroy", "rw_last_error", "rw_reset", "rw_step", "rw_step_device",
-    "rw_step_many_device", "rw_step_tape_device", "rw_step_tape_device_timed", "rw_refresh_obs", "rw_refresh_grid", "rw_mark_views_stale", "rw_set_stream", "rw_jit_log", "rw_jit_probe", "rw_multi_create", "rw_multi_step_device", "rw_multi_destroy", "rw_sync", "rw_get_buffer", "rw_read", "rw_read_outputs", "rw_write",
+    "rw_step_many_device", "rw_step_tape_device", "rw_step_tape_device_timed", "rw_refresh_obs", "rw_unpack_obs", "rw_refresh_grid", "rw_mark_views_stale", "rw_set_stream", "rw_jit_log", "rw_jit_probe", "rw_multi_create", "rw_multi_step_device", "rw_multi_destroy", "rw_sync", "rw_get_buffer", "rw_read", "rw_read_outputs", "rw_write",
     "rw_recalc_grid", "rw_get_info", "rw_seed_state", "rw_event_record", "rw_event_elapsed_ms",
     "rw_abi_version", "rw_debug_timeline", "rw_debug_store_floor", "rw_device_malloc", "rw_device_free", "rw_copy_to_device",
     "rw_copy_to_host", "rw_selftest", "rw_snapshot_create", "rw_snapshot_save", "rw_snapshot_restore", "rw_snapshot_destroy",
@@ -114,6 +117,7 @@ def load(path: str | None = None):
     lib.rw_step_tape_device.argtypes = [vp, vp, i32, i32, i32]
     lib.rw_step_tape_device_timed.argtypes = [vp, vp, i32, i32, i32, i32, i32]
     lib.rw_refresh_obs.argtypes = [vp]
+    lib.rw_unpack_obs.argtypes = [vp, vp, vp, C.c_int64]
     lib.rw_refresh_grid.argtypes = [vp]
     lib.rw_mark_views_stale.argtypes = [vp]
     lib.rw_set_stream.argtypes = [vp, vp]
@@ -188,7 +192,7 @@ class Engine:
                  max_inactivity_steps, max_steps, reward_type, normalised_coordinates=False,
                  autoreset_mode="next_step", device_id=0, envs_per_workgroup=0,
                  threads_per_workgroup=0, stream=None, library=None, observation_type=1,
-                 image_layers=(), image_directional=True, msg_bits=0, use_given_stream=False, obs_stores=None, jit=None, pipe=None, stats=False, wave_priority=None):
+                 image_layers=(), image_directional=True, msg_bits=0, use_given_stream=False, obs_stores=None, jit=None, pipe=None, stats=False, wave_priority=None, obs_packed=False):
         self.lib = load(library)
         self._h = C.c_void_p()
         self._arena, self.arena_allocations = {}, 0  # rollout_host's device tapes (grow-only; freed in close())
@@ -204,7 +208,7 @@ class Engine:
             (RW_STREAM_USE_GIVEN if use_given_stream else 0) | {None: 0, "auto": 0, "cached": RW_OBS_STORES_CACHED, "stream": RW_OBS_STORES_STREAM}[obs_stores]
             | {None: 0, "auto": 0, False: RW_JIT_OFF, "off": RW_JIT_OFF, True: RW_JIT_FORCE, "force": RW_JIT_FORCE}[jit]
             | {None: 0, "auto": 0, False: RW_PIPE_OFF, "off": RW_PIPE_OFF, True: RW_PIPE_ON, "on": RW_PIPE_ON}[pipe]
-            | (RW_STATS_ON if stats else 0)
+            | (RW_STATS_ON if stats else 0) | (RW_OBS_PACKED if obs_packed else 0)
             | {None: 0, "auto": 0, False: RW_PRIO_OFF, "off": RW_PRIO_OFF, True: RW_PRIO_ON, "on": RW_PRIO_ON}[wave_priority],
             hw.ctypes.data, goals.ctypes.data, C.c_void_p(stream or 0))
         rc = self.lib.rw_create(C.byref(cfg), C.byref(self._h))
@@ -229,6 +233,11 @@ class Engine:
             "stat_deliveries": (self.B,), "stat_failed_moves": (self.B,),
         }
         self.stats = bool(i.stats)
+        # obs_packed=True (RW_OBS_PACKED): the launches write uint32 rows of PW words to "obs_packed"; "obs" does not exist
+        self.packed = bool(i.obs_packed)
+        self.PW = 1 + (self.L + 31) // 32 if int(observation_type) == 1 else 0
+        self.shapes["obs_packed"] = (self.B, self.N, self.PW)
+        self.obs_name = "obs_packed" if self.packed else "obs"  # the observation buffer the launches write
 
     def _check(self, rc):
         if rc != RW_OK:
@@ -286,7 +295,7 @@ class Engine:
         (obs (T,B,N,L) or None, rewards (T,B,N), terminated (T,B))."""
         a = np.ascontiguousarray(actions, dtype=np.int32).reshape(-1, self.B, self.N * (1 + self.M))
         T = a.shape[0]
-        obs = np.empty((T,) + self.shapes["obs"], np.float32) if want_obs else None
+        obs = np.empty((T,) + self.shapes[self.obs_name], BUF_DTYPE[self.obs_name]) if want_obs else None  # (packed: uint32 (T,B,N,PW))
         rew = np.empty((T, self.B, self.N), np.float32)
         term = np.empty((T, self.B), np.uint8)
         # device tapes from the engine's arena: grow-only buffers kept for the engine's lifetime, so a training loop that
@@ -364,22 +373,32 @@ class Engine:
 
     def read_outputs(self, want_features=False):
         """obs, rewards, terminated (uint8), features-or-None as fresh host arrays: one C call, one synchronisation."""
-        obs = np.empty(self.shapes["obs"], np.float32)
+        obs = None if self.packed else np.empty(self.shapes["obs"], np.float32)
         rew = np.empty(self.shapes["rewards"], np.float32)
         term = np.empty(self.shapes["terminated"], np.uint8)
         feat = np.empty(self.shapes["features"], np.float32) if want_features else None
-        self._check(self.lib.rw_read_outputs(self._h, obs.ctypes.data, rew.ctypes.data, term.ctypes.data,
+        self._check(self.lib.rw_read_outputs(self._h, None if self.packed else obs.ctypes.data, rew.ctypes.data, term.ctypes.data,
                                              feat.ctypes.data if want_features else None))
+        if self.packed:  # (rw_read_outputs speaks float32: the packed rows are 1 / 18 of them, one more small copy)
+            obs = self.read("obs_packed")
         return obs, rew, term, feat
 
     def write(self, name, array):
         a = np.ascontiguousarray(array, dtype=BUF_DTYPE.get(name, np.int32)).reshape(self.shapes[name])
         self._check(self.lib.rw_write(self._h, BUF[name], a.ctypes.data, a.nbytes))
 
-    def device_array(self, name) -> DeviceArray:
+    def unpack_obs_device(self, packed_ptr, out_ptr, n_rows):
+        """rw_unpack_obs: `n_rows` packed rows (device uint32 [n_rows][PW]) -> float32 [n_rows][L] at `out_ptr`, on the engine's stream."""
+        self._check(self.lib.rw_unpack_obs(self._h, C.c_void_p(int(packed_ptr)), C.c_void_p(int(out_ptr)), int(n_rows)))
+
+    def device_array(self, name, dtype=None) -> DeviceArray:
+        """`dtype`: present the buffer as another dtype of the same width ("obs_packed" as int32 for torch, whose uint32 has no shift ops)."""
         ptr, nbytes = C.c_void_p(), C.c_size_t()
         self._check(self.lib.rw_get_buffer(self._h, BUF[name], C.byref(ptr), C.byref(nbytes)))
-        return DeviceArray(ptr.value or 0, self.shapes[name], BUF_DTYPE.get(name, np.int32), self)
+        if name in ("obs", "obs_packed") and not nbytes.value:
+            raise RuntimeError('this engine writes packed observations (obs_format="packed"): there is no float32 "obs" buffer — use "obs_packed" and unpack_obs'
+                               if name == "obs" else 'this engine writes float32 observations: "obs_packed" exists only with obs_format="packed"')
+        return DeviceArray(ptr.value or 0, self.shapes[name], dtype or BUF_DTYPE.get(name, np.int32), self)
 
     def recalc_grid(self, shelf_xy):
         s = np.ascontiguousarray(shelf_xy, dtype=np.int32).reshape(self.B, -1, 2)
@@ -453,13 +472,13 @@ def seed_state(seed: int, library=None) -> np.ndarray:
     return out
 
 
-def jit_probe(*, sensor_range, H, W, N, Q, S, E, msg_bits=0, obs=0, layers=(), directional=True, nt=1, arch="gfx950", library=None):
+def jit_probe(*, sensor_range, H, W, N, Q, S, E, msg_bits=0, obs=0, layers=(), directional=True, nt=1, packed=0, arch="gfx950", library=None):
     """Compile (or find cached) the run-time specialised build of a shape without a device; returns (code bytes or -1, log)."""
-    packed = 0
+    layer_bits = 0
     for k, l in enumerate(layers):
-        packed |= int(l) << (4 * k)
-    shape = (C.c_int32 * 15)(sensor_range, H, W, N, Q, S, E, 256, msg_bits, 1 if S > 255 else 0, obs, len(layers), packed,
-                             (1 if directional else 0) if obs == 1 else -1, nt)
+        layer_bits |= int(l) << (4 * k)
+    shape = (C.c_int32 * 16)(sensor_range, H, W, N, Q, S, E, 256, msg_bits, 1 if S > 255 else 0, obs, len(layers), layer_bits,
+                             (1 if directional else 0) if obs == 1 else -1, nt, int(packed))
     log = C.create_string_buffer(4096)
     n = load(library).rw_jit_probe(shape, arch.encode(), log, 4096)
     return int(n), log.value.decode(errors="replace")

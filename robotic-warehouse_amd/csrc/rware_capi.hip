@@ -102,6 +102,9 @@ struct rw_engine {
     bool wide = false;
     bool image = false;        // IMAGE / IMAGE_DICT observation kernels
     bool stats = false;        // RW_STATS_ON: every launch carries OP_FLAG_STATS, RW_BUF_STAT_* are allocated
+    bool packed = false;       // RW_OBS_PACKED: every launch carries OP_FLAG_PACKED and writes uint32 rows to RW_BUF_OBS_PACKED; RW_BUF_OBS is empty
+    int PW = 0;                // words of a packed row, 1 + ceil(L / 32) (FLATTENED; 0 for the IMAGE types)
+    int row_words = 0;         // dwords per agent of the observation the launches write: L floats, or PW words when packed
     int msg_bits = 0;          // communication bits per agent (FLATTENED only)
     int32_t *d_status = nullptr;
     hipEvent_t events[8]{};
@@ -109,6 +112,61 @@ struct rw_engine {
     std::string err;
     hipDeviceProp_t prop{};
 };
+
+// rw_unpack_obs: packed rows uint32 [n_rows][PW] -> float32 [n_rows][L], bit for bit what RW_BUF_OBS would hold.  One thread per float4
+// of the output.  A float4 that lies inside the bit part of one row (all but ~2 in 18 at sensor_range 1) takes its four bits from one
+// or two packed words, spreads them into four bytes with one multiply (bit j -> byte j) and converts each byte (v_cvt_f32_ubyteN), as
+// the step kernel's expansion does; one that holds a coordinate slot or straddles two rows goes element by element.  The output is a
+// pure stream: non-temporal stores.  `aligned`: the output starts on a 16-byte boundary (else scalar stores).
+namespace rw {
+__device__ __forceinline__ float unpack_elem(const uint32_t *__restrict__ packed, size_t row, int k, int PW, int W, int H, int normalised) {
+    const uint32_t *r = packed + row * (size_t)PW;
+    if (k < 2) {
+        const int v = (int)(k == 0 ? (r[0] & 0xFFFFu) : (r[0] >> 16));
+        if (normalised) return (float)((double)v / (double)((k == 0 ? W : H) - 1));  // coordf of the step kernel (rware/warehouse.py:636-638)
+        return (float)v;
+    }
+    return ((r[1 + (k >> 5)] >> (k & 31)) & 1u) ? 1.0f : 0.0f;
+}
+template <typename Dummy = void>
+__global__ void __launch_bounds__(256) rware_unpack_obs_kernel(const uint32_t *__restrict__ packed, float *__restrict__ out, size_t n_floats,
+                                                                int L, int PW, int W, int H, int normalised, int aligned) {
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t f = q << 2;
+    if (f >= n_floats) return;
+    const size_t row = f / (size_t)L;
+    const int k = (int)(f - row * (size_t)L);
+    if (aligned && k >= 2 && k + 3 < L && f + 3 < n_floats) {
+        const uint32_t *r = packed + row * (size_t)PW + 1 + (k >> 5);
+        const int sh = k & 31;
+        const uint32_t lo = r[0], hi = sh > 28 ? r[1] : 0u;  // (sh > 28 implies k + 3 crosses into the next word, which the row still owns: k + 3 < L)
+        const uint32_t nib = funnel_shr(lo, hi, (uint32_t)sh) & 0xFu;
+        const uint32_t b = opaque((nib * 0x00204081u) & 0x01010101u);
+        float4 v;
+        v.x = (float)(b & 0xFFu);
+        v.y = (float)((b >> 8) & 0xFFu);
+        v.z = (float)((b >> 16) & 0xFFu);
+        v.w = (float)(b >> 24);
+        store_f4_nt(reinterpret_cast<float4 *>(out + f), v);
+        return;
+    }
+    float e[4];
+    size_t rw_ = row;
+    int kk = k;
+    const int n = (int)(n_floats - f < 4 ? n_floats - f : 4);
+    for (int j = 0; j < n; ++j) {
+        e[j] = unpack_elem(packed, rw_, kk, PW, W, H, normalised);
+        if (++kk == L) { kk = 0; ++rw_; }
+    }
+    if (aligned && n == 4) {
+        float4 v;
+        v.x = e[0]; v.y = e[1]; v.z = e[2]; v.w = e[3];
+        store_f4_nt(reinterpret_cast<float4 *>(out + f), v);
+    } else {
+        for (int j = 0; j < n; ++j) out[f + j] = e[j];
+    }
+}
+}  // namespace rw
 
 namespace {
 
@@ -162,6 +220,7 @@ int launch(rw_engine *eng, rw::LaunchArgs la, int op, bool rollout = false, hipE
     const bool pipe = eng->pipe.fn && op == rw::OP_STEP && !rollout;  // (persistent workgroups: no start stagger)
     if (!pipe) la.op |= (k.stagger_ticks & 0xff) << 16 | (k.stagger_shift & 0xf) << 24;
     if (eng->stats) la.op |= rw::OP_FLAG_STATS;
+    if (eng->packed) la.op |= rw::OP_FLAG_PACKED;
     if (k.prio) la.op |= rw::OP_FLAG_PRIO;
     if (op != rw::OP_OBS) eng->grid_stale = eng->agents_stale = eng->counters_stale = true;  // the kernels keep the shadow and the packed agent records current, not the int32 views
     if (!eng->own_stream && !eng->captured) {  // (a stream of the caller's may be capturing; the engine's own stream never is)
@@ -287,6 +346,7 @@ int pack_counters(rw_engine *eng) {
 size_t elem_size(int kind) {
     switch (kind) {
         case RW_BUF_OBS: case RW_BUF_REWARDS: case RW_BUF_FEATURES: case RW_BUF_FINAL_OBS: case RW_BUF_FINAL_FEATURES: return 4;
+        case RW_BUF_OBS_PACKED: return 4;  // uint32 words
         case RW_BUF_TERMINATED: case RW_BUF_TRUNCATED: case RW_BUF_NEED_RESET: return 1;
         case RW_BUF_RNG: return 8;
         default: return 4;
@@ -299,6 +359,9 @@ size_t elem_size(int kind) {
 struct Shape {
     int B, H, W, N, Q, S, R, HW, SW;
     int L;       // floats per agent in RW_BUF_OBS
+    bool packed; // RW_OBS_PACKED: the launches write uint32 rows of PW words instead (RW_BUF_OBS_PACKED)
+    int PW;      // words of a packed row: 1 + ceil(L / 32) (FLATTENED)
+    int row_words() const { return packed ? PW : L; }  // dwords per agent of the observation a step writes
     int OW;      // LDS bit-string words per agent (must equal the kernel's OW): the flattened row, or n_layers image planes
     int M, AM;   // communication bits per agent (FLATTENED only); action words per agent
     int n_layers, layers[8];
@@ -363,6 +426,13 @@ int check_config(const rw_config *cfg, Shape *out) {
     const int CELLS = (2 * s.R + 1) * (2 * s.R + 1);
     s.L = s.image ? s.n_layers * CELLS : 8 + (7 + s.M) * CELLS;
     s.OW = s.image ? std::max((8 + 7 * CELLS + 31) / 32, (s.n_layers * CELLS + 31) / 32) : (8 + (7 + s.M) * CELLS + 31) / 32;
+    s.packed = (cfg->stream_flags & RW_OBS_PACKED) != 0;
+    s.PW = s.image ? 0 : 1 + (s.L + 31) / 32;
+    if (s.packed && s.image)  // (the AGENT_DIRECTION layer holds dir + 1: an image is not a string of bits)
+        return fail(nullptr, RW_ERR_UNSUPPORTED, "RW_OBS_PACKED: only FLATTENED observations are bits (plus two coordinates); "
+                    "the IMAGE types are not packed (AGENT_DIRECTION holds dir + 1)");
+    if (s.packed && (W > 65535 || H > 65535))  // (H*W <= 10000 excludes it already: the format's own limit, kept explicit)
+        return fail(nullptr, RW_ERR_UNSUPPORTED, "RW_OBS_PACKED: a packed row holds x | y << 16: grids up to 65535 cells a side");
     *out = s;
     return RW_OK;
 }
@@ -387,6 +457,9 @@ int init_engine(rw_engine *eng, const rw_config *cfg, const Shape &s) {
     eng->L = s.L;
     eng->OW = s.OW;
     eng->stats = (cfg->stream_flags & RW_STATS_ON) != 0;
+    eng->packed = s.packed;
+    eng->PW = s.PW;
+    eng->row_words = s.row_words();
     RW_HIP_CREATE(hipSetDevice(cfg->device_id));
     RW_HIP_CREATE(hipGetDeviceProperties(&eng->prop, cfg->device_id));
     if (cfg->stream || (cfg->stream_flags & RW_STREAM_USE_GIVEN)) {
@@ -445,9 +518,11 @@ bool serves(const StaticEntry &se, const Shape &s) {
 // that size (large-16ag r=2 B = 16384 37.3 -> 43.7; small-19ag 28.9 vs 27.6 cached; large-16ag r=1: even).
 // (by chunk size in floats: 4544 small-4ag, 6816 small-12ag at 8 envs: the hint wins; 9088 large-16ag: even; 10792 small-19ag,
 //  23424 large-16ag r=2: it loses below the cache size; 9656 small-17ag: 26.1 vs 25.5 cached)
+// RW_OBS_PACKED: the rule is fed the packed chunk and step sizes (dwords) — the thresholds are INHERITED from the float rows, not
+// re-measured: with rows 18 x smaller every registered task lands on "small chunk", i.e. on the hint.
 bool nt_rule(const rw_config *cfg, const Shape &s, int E) {
-    const long long chunk = (long long)E * s.N * s.L;  // floats of one workgroup's observations
-    const double obs_mb = (double)s.B * s.N * s.L * 4 / 1e6;
+    const long long chunk = (long long)E * s.N * s.row_words();  // floats (packed: words) of one workgroup's observations
+    const double obs_mb = (double)s.B * s.N * s.row_words() * 4 / 1e6;
     // (A/B hook RWARE_OBS_STORES: moves the default only — an explicit flag of the caller wins)
     const int mode = tri_state(cfg, "RWARE_OBS_STORES", "cached", "stream", RW_OBS_STORES_CACHED, RW_OBS_STORES_STREAM);
     return mode ? mode > 0 : chunk <= 9500 || obs_mb > 240.0;
@@ -464,6 +539,10 @@ struct Build {
     bool wide4 = false;      // 9 .. 19 agents on the 4-env per-step build (read for 13 .. 16: priority instead of the start stagger)
     bool q_runtime = false;  // the build reads the request-queue length at run time (StaticEntry::Q == -1)
     int kind = 0;            // rw_info::build_kind
+    // RW_OBS_PACKED: the geometry of the ahead-of-time specialised build this shape would run without the flag (pick_static found it and
+    // may not use it): the run-time packed build takes the same envs per workgroup — and the 4-env rule of 9 .. 19 agents with it
+    int aot_E = 0;
+    bool aot_wide4 = false;
 };
 
 // A specialised build of the table: exact-shape entries before size-static ones, first match wins; the 4-env rule of 9 .. 19 agents;
@@ -524,6 +603,14 @@ void pick_static(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *b)
         best = nullptr;
         eng->jit_log = "event counters: the ahead-of-time exact-shape builds do not carry the counting code";
     }
+    // packed observation rows (RW_OBS_PACKED): never an ahead-of-time specialised build — the generic kernel, or a run-time compiled
+    // exact-shape build made with RW_PACKED_BUILD (try_jit_build)
+    if (best && eng->packed) {
+        if (best->T == 256) { b->aot_E = best->E; b->aot_wide4 = want_e == 4; }
+        best = nullptr;
+        eng->jit_log = (eng->jit_log.empty() ? std::string() : eng->jit_log + " | ") +
+                       "packed observations: the ahead-of-time exact-shape builds do not carry the packed rows";
+    }
     if (!best) return;
     b->E = best->E;
     b->T = best->T;
@@ -554,6 +641,8 @@ int pick_build(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *b) {
         return fail(eng, RW_ERR_INVALID_ARG, "envs_per_workgroup %d too large for N=%d Q=%d", E, s.N, s.Q);
     if (eng->stats && !rw_tab::generic_has_stats())
         return fail(eng, RW_ERR_UNSUPPORTED, "RW_STATS_ON: this library was built without the event-counter code (RW_STATS_BUILD)");
+    if (eng->packed && !rw_tab::generic_has_packed())
+        return fail(eng, RW_ERR_UNSUPPORTED, "RW_OBS_PACKED: this library was built without the packed observation rows (RW_PACKED_BUILD)");
     using pick_t = step_kernel_t (*)(bool, bool, bool, bool);
     static const pick_t kGeneric[5] = {rw_tab::generic_r1, rw_tab::generic_r2, rw_tab::generic_r3, rw_tab::generic_r4, rw_tab::generic_r5};
     const pick_t pick = kGeneric[(s.R < 1 ? 1 : s.R > 5 ? 5 : s.R) - 1];
@@ -582,6 +671,8 @@ void try_jit_build(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *
     else if (N <= 2) { prefs[0] = B >= 16384 ? 32 : 16; prefs[1] = 16; prefs[2] = 8; prefs[3] = 4; }
     else if (N <= 4) { prefs[0] = 16; prefs[1] = 8; prefs[2] = 4; }
     else if (N <= 8) { prefs[0] = B <= 16384 ? 8 : 16; prefs[1] = B <= 16384 ? 16 : 8; prefs[2] = 4; }
+    // a packed engine: first the geometry its float twin runs on (the ahead-of-time entry pick_static chose), then the list above
+    if (!geom_given && b->aot_E) { for (int k = 4; k > 0; --k) prefs[k] = prefs[k - 1]; prefs[0] = b->aot_E; }
     int je = 0;
     for (int k = 0; k < 5 && !je; ++k) {
         const int c = prefs[k];
@@ -606,6 +697,7 @@ void try_jit_build(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *
     sh.layers = s.image ? s.packed_layers() : 0;
     sh.nt = nt_rule(cfg, s, je) ? 1 : 0;
     sh.stats = eng->stats ? 1 : 0;
+    sh.packed = eng->packed ? 1 : 0;
     // (two attempts: a CACHED code object the runtime refuses — a truncated or foreign file behind a well-formed header — is
     //  dropped from the cache and the shape compiled afresh, once; otherwise every later construction would trip over it)
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -619,7 +711,10 @@ void try_jit_build(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *
         if (me == hipSuccess) me = hipModuleGetFunction(&fs, eng->jit_module, res.step_name.c_str());
         if (me == hipSuccess) me = hipModuleGetFunction(&fr, eng->jit_module, res.rollout_name.c_str());
         if (me == hipSuccess) {
+            const int aot_E = b->aot_E;
+            const bool aot_wide4 = b->aot_wide4;
             *b = Build{};
+            b->wide4 = aot_wide4 && je == aot_E;   // (read by plan_launches for 13 .. 16 agents: priority instead of the start stagger)
             b->jit_step = fs;
             b->jit_rollout = fr;
             b->jit_nt = sh.nt;
@@ -683,7 +778,7 @@ int plan_launches(rw_engine *eng, const rw_config *cfg, const Shape &s, const Bu
     // The fused rollouts (every step of the launch raises the priority again): they gain at every agent count — small-4ag 3.95 ->
     // 3.72 us per step, medium-6ag-hard x 8192 4.20 -> 3.94, small-8ag 8.89 -> 8.33, medium-13ag 14.5 -> 13.85, large-16ag 21.75 -> 21.25
     // (profiles/r06_prio_rollout.txt) — so only the size limit applies to them.
-    const bool fits = (double)s.B * N * s.L * 4 <= 200e6;
+    const bool fits = (double)s.B * N * s.row_words() * 4 <= 200e6;  // (packed rows: their own size; the limit is the float rows')
     // (13 .. 16 agents — `wide4` below is only ever read for them: on their 4-env workgroups with the priority; on 8-env workgroups — the tiny warehouse has no 4-env build — with it
     //  only up to half a round of workgroups, where the stagger is a loss: 4096 envs large-16ag 9.52 us with the stagger, 9.00 without,
     //  8.80 with the priority instead; 8192: small-14ag 12.65 / 11.26 / 10.84; profiles/r06_1316_matrix.txt)
@@ -730,7 +825,7 @@ void pick_pipe(rw_engine *eng, const rw_config *cfg, const Shape &s) {
     const char *pee = rw_hook("RWARE_PIPE_E");
     const int want_e = pee ? atoi(pee) : 0;
     const StaticEntry *pb = nullptr;
-    if (mode >= 0 && !s.image && s.M == 0 && !eng->step.jit && !(eng->stats && !rw_tab::static_has_stats()))
+    if (mode >= 0 && !s.image && s.M == 0 && !eng->step.jit && !(eng->stats && !rw_tab::static_has_stats()) && !eng->packed)
         pb = find_static([&](const StaticEntry &se) { return se.pipe && se.N == s.N && serves(se, s) && (!want_e || se.E == want_e); });
     if (pb) {
         const int n_cu = eng->prop.multiProcessorCount;
@@ -760,6 +855,8 @@ void pick_pipe(rw_engine *eng, const rw_config *cfg, const Shape &s) {
     if (mode == 1 && !eng->pipe.fn) {  // asked for and not available: say so where rw_get_info().pipe_workgroups == 0 sends the caller (rw_jit_log)
         if (!eng->jit_log.empty()) eng->jit_log += " | ";
         eng->jit_log += "pipe: RW_PIPE_ON requested, the classic kernel runs: ";
+        if (eng->packed) eng->jit_log += "packed observations (RW_OBS_PACKED) are served by the classic kernels only";
+        else
 #if RW_WITH_PIPE
         eng->jit_log += pb ? "the pipelined build of this shape does not fit (LDS / occupancy)"
                            : "no pipelined build for this shape (FLATTENED without messages, ahead-of-time builds, batch a multiple of its chunk size)";
@@ -774,7 +871,9 @@ int alloc_state(rw_engine *eng, const rw_config *cfg, const Shape &s) {
     const int N = s.N, HW = s.HW, Q = s.Q;
     const size_t szB = (size_t)s.B;
     size_t n_elems[RW_BUF_KIND_COUNT];
-    n_elems[RW_BUF_OBS] = szB * N * eng->L;
+    // RW_OBS_PACKED: the float rows are neither streamed nor held (298 MB at 262144 small-4ag envs) — RW_BUF_OBS is empty then
+    n_elems[RW_BUF_OBS] = eng->packed ? 0 : szB * N * eng->L;
+    n_elems[RW_BUF_OBS_PACKED] = eng->packed ? szB * N * eng->PW : 0;
     n_elems[RW_BUF_REWARDS] = szB * N;
     n_elems[RW_BUF_TERMINATED] = szB;
     n_elems[RW_BUF_TRUNCATED] = szB;
@@ -800,7 +899,7 @@ int alloc_state(rw_engine *eng, const rw_config *cfg, const Shape &s) {
     static const int order[RW_BUF_KIND_COUNT] = {
         RW_BUF_AGENT_X, RW_BUF_AGENT_Y, RW_BUF_AGENT_DIR, RW_BUF_AGENT_CARRY, RW_BUF_AGENT_DELIVERED, RW_BUF_QUEUE,
         RW_BUF_AGENT_MSG, RW_BUF_STEPS, RW_BUF_INACTIVE, RW_BUF_NEED_RESET, RW_BUF_REWARDS, RW_BUF_TERMINATED, RW_BUF_TRUNCATED,
-        RW_BUF_STAT_DELIVERIES, RW_BUF_STAT_FAILED_MOVES, RW_BUF_ACTIONS, RW_BUF_RNG, RW_BUF_FEATURES, RW_BUF_OBS, RW_BUF_FINAL_OBS, RW_BUF_FINAL_FEATURES, RW_BUF_GRID};
+        RW_BUF_STAT_DELIVERIES, RW_BUF_STAT_FAILED_MOVES, RW_BUF_ACTIONS, RW_BUF_RNG, RW_BUF_FEATURES, RW_BUF_OBS, RW_BUF_OBS_PACKED, RW_BUF_FINAL_OBS, RW_BUF_FINAL_FEATURES, RW_BUF_GRID};
     auto up = [](size_t x) { return (x + 4095) & ~(size_t)4095; };
     size_t slab_bytes = 0, off[RW_BUF_KIND_COUNT];
     eng->rec_off = 0;  // the packed agent records lead the hot set, the counter records follow
@@ -897,7 +996,7 @@ int fill_params(rw_engine *eng, const rw_config *cfg, const Shape &s) {
     rw::LaunchArgs &la = eng->la;
     la.actions = (const int32_t *)eng->buf[RW_BUF_ACTIONS].ptr;
     la.reset_mask = eng->d_mask;
-    la.obs = (float *)eng->buf[RW_BUF_OBS].ptr;
+    la.obs = (float *)eng->buf[eng->packed ? RW_BUF_OBS_PACKED : RW_BUF_OBS].ptr;  // (packed: uint32 rows through the same slot)
     la.rewards = (float *)eng->buf[RW_BUF_REWARDS].ptr;
     la.terminated = (uint8_t *)eng->buf[RW_BUF_TERMINATED].ptr;
     la.timeline = nullptr;
@@ -1111,7 +1210,7 @@ int rw_step_many_device(rw_engine *eng, const int32_t *actions_dev, int32_t n_st
     la.actions = actions_dev;
     la.n_steps = n_steps;
     la.act_stride = (int64_t)BN * (1 + eng->msg_bits);
-    if (obs_tape) { la.obs = obs_tape; la.obs_stride = (int64_t)(BN * eng->L); }
+    if (obs_tape) { la.obs = obs_tape; la.obs_stride = (int64_t)(BN * eng->row_words); }  // (packed: uint32 [T][B][N][PW], in words)
     if (reward_tape) { la.rewards = reward_tape; la.rew_stride = (int64_t)BN; }
     if (terminated_tape) { la.terminated = terminated_tape; la.term_stride = (int64_t)eng->prm.B; }
     return launch(eng, la, rw::OP_STEP, /*rollout=*/true);
@@ -1149,9 +1248,9 @@ int rw_debug_store_floor(rw_engine *eng, int32_t n_launches, float *ms_per_launc
     // the practical floor beside the 8 TB/s one (bench.py `roofline.store_only_*`).  RW_BUF_OBS is refreshed afterwards.
     if (!eng || n_launches < 1 || !ms_per_launch) return RW_ERR_INVALID_ARG;
     RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    const int per_wg = eng->step.E * eng->prm.N * eng->L;  // floats
-    float *obs = (float *)eng->buf[RW_BUF_OBS].ptr;
-    const size_t total = (size_t)eng->prm.B * eng->prm.N * eng->L;  // (size_t, like the step kernel's offsets: past 2^31 floats for large batches)
+    const int per_wg = eng->step.E * eng->prm.N * eng->row_words;  // floats (RW_OBS_PACKED: the words of the packed rows — that engine's stream)
+    float *obs = eng->la.obs;
+    const size_t total = (size_t)eng->prm.B * eng->prm.N * eng->row_words;  // (size_t, like the step kernel's offsets: past 2^31 floats for large batches)
     for (int k = 0; k < n_launches; ++k) {
         hipEvent_t a = k == 0 ? eng->events[6] : nullptr, b = k == n_launches - 1 ? eng->events[7] : nullptr;
         if (eng->prm.nt_obs)
@@ -1209,6 +1308,7 @@ namespace {
 // the state that reset()/step() evolve: (device pointer, size) pieces in a fixed order
 std::vector<std::pair<void *, size_t>> state_pieces(rw_engine *eng) {
     static const int kinds[] = {RW_BUF_QUEUE, RW_BUF_RNG, RW_BUF_AGENT_MSG, RW_BUF_STAT_DELIVERIES, RW_BUF_STAT_FAILED_MOVES};  // (the last two: empty without RW_STATS_ON)
+    // (RW_BUF_OBS / RW_BUF_OBS_PACKED are outputs, not state: a restore recomputes them, OP_OBS, in the engine's format)
     std::vector<std::pair<void *, size_t>> v;
     v.emplace_back(eng->d_rec, (size_t)eng->prm.B * eng->prm.N * sizeof(uint32_t));  // the agents: their packed records
     v.emplace_back(eng->d_cnt, (size_t)eng->prm.B * 2 * sizeof(int32_t));            // steps, inactive, pending resets: the counter records
@@ -1273,6 +1373,21 @@ int rw_refresh_obs(rw_engine *eng) {
     return launch(eng, eng->la, rw::OP_OBS);
 }
 
+int rw_unpack_obs(rw_engine *eng, const uint32_t *packed_dev, float *obs_f32_dev, int64_t n_rows) {
+    if (!eng || n_rows < 0 || (n_rows && (!packed_dev || !obs_f32_dev))) return RW_ERR_INVALID_ARG;
+    if (eng->image) return fail(eng, RW_ERR_UNSUPPORTED, "rw_unpack_obs: packed rows exist for FLATTENED observations only");
+    if (n_rows == 0) return RW_OK;
+    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
+    const size_t n_floats = (size_t)n_rows * (size_t)eng->L, n_q = (n_floats + 3) / 4;
+    const size_t blocks = (n_q + 255) / 256;
+    if (blocks > 0x7fffffffu) return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs: %lld rows are more than one launch holds; unpack in slices", (long long)n_rows);
+    const int aligned = (reinterpret_cast<uintptr_t>(obs_f32_dev) & 15u) == 0 ? 1 : 0;
+    hipLaunchKernelGGL((rw::rware_unpack_obs_kernel<>), dim3((unsigned)blocks), dim3(256), 0, eng->stream, packed_dev, obs_f32_dev, n_floats,
+                       eng->L, eng->PW, eng->prm.W, eng->prm.H, eng->prm.normalised, aligned);
+    RW_HIP(eng, hipGetLastError());
+    return RW_OK;
+}
+
 int rw_sync(rw_engine *eng) {
     if (!eng) return RW_ERR_INVALID_ARG;
     RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
@@ -1293,7 +1408,7 @@ int rw_sync(rw_engine *eng) {
 
 const char *rw_jit_log(const rw_engine *eng) { return eng ? eng->jit_log.c_str() : ""; }
 
-int64_t rw_jit_probe(const int32_t shape[15], const char *arch, char *log, size_t log_len) {
+int64_t rw_jit_probe(const int32_t shape[16], const char *arch, char *log, size_t log_len) {
     // Compiles (or finds in the disk cache) the exact-shape build of `shape` for `arch` WITHOUT a device: the compile half of
     // what rw_create does for a shape with no ahead-of-time build.  Returns the size of the code object, or -1.
     if (!shape || !arch) return -1;
@@ -1302,6 +1417,7 @@ int64_t rw_jit_probe(const int32_t shape[15], const char *arch, char *log, size_
     sh.R = shape[0]; sh.H = shape[1]; sh.W = shape[2]; sh.N = shape[3]; sh.Q = shape[4]; sh.S = shape[5]; sh.E = shape[6]; sh.T = shape[7];
     sh.M = shape[8]; sh.wide = shape[9]; sh.obs = shape[10]; sh.NL = shape[11]; sh.layers = (uint32_t)shape[12]; sh.directional = shape[13];
     sh.nt = shape[14];
+    sh.packed = shape[15];
     rw_jit::Result res;
     const bool ok = rw_jit::compile(sh, arch, &res);
     if (log && log_len) snprintf(log, log_len, "%s", res.log.c_str());
@@ -1328,6 +1444,7 @@ int rw_set_stream(rw_engine *eng, void *stream) {
 int rw_mark_views_stale(rw_engine *eng) {
     if (!eng) return RW_ERR_INVALID_ARG;
     eng->grid_stale = eng->agents_stale = eng->counters_stale = true;  // (every derived view: grid, the five agent arrays, steps / inactive / need_reset)
+    // (RW_BUF_OBS_PACKED is no derived view: the launches write it themselves, a replayed graph included — nothing to mark)
     return RW_OK;
 }
 
@@ -1346,13 +1463,18 @@ int rw_get_buffer(rw_engine *eng, int kind, void **dev_ptr, size_t *bytes) {
         const int rc = kind == RW_BUF_GRID ? refresh_grid(eng) : is_agent_view(kind) ? refresh_agents(eng) : refresh_counters(eng);
         if (rc != RW_OK) return rc;
     }
-    if (dev_ptr) *dev_ptr = eng->buf[kind].ptr;
+    // (an observation buffer in the format this engine does not produce — RW_BUF_OBS with RW_OBS_PACKED, RW_BUF_OBS_PACKED without — is
+    //  empty: no pointer, 0 bytes)
+    const bool absent = (kind == RW_BUF_OBS || kind == RW_BUF_OBS_PACKED) && eng->buf[kind].bytes == 0;
+    if (dev_ptr) *dev_ptr = absent ? nullptr : eng->buf[kind].ptr;
     if (bytes) *bytes = eng->buf[kind].bytes;
     return RW_OK;
 }
 
 int rw_read(rw_engine *eng, int kind, void *host_dst, size_t bytes) {
     if (!eng || kind < 0 || kind >= RW_BUF_KIND_COUNT || (!host_dst && bytes)) return RW_ERR_INVALID_ARG;
+    if (kind == RW_BUF_OBS && eng->packed)
+        return fail(eng, RW_ERR_UNSUPPORTED, "rw_read: RW_BUF_OBS does not exist with RW_OBS_PACKED (read RW_BUF_OBS_PACKED, or rw_unpack_obs on the device)");
     if (bytes != eng->buf[kind].bytes)
         return fail(eng, RW_ERR_INVALID_ARG, "rw_read kind %d: %zu bytes given, buffer holds %zu", kind, bytes, eng->buf[kind].bytes);
     RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
@@ -1369,6 +1491,8 @@ int rw_read_outputs(rw_engine *eng, float *obs, float *rewards, uint8_t *termina
     // what step() returns, in ONE round trip: the copies are enqueued back to back and waited for once (four rw_read calls
     // are four synchronisations — 137 us per step at B = 1024 where the kernel takes 5)
     if (!eng) return RW_ERR_INVALID_ARG;
+    if (obs && eng->packed)
+        return fail(eng, RW_ERR_UNSUPPORTED, "rw_read_outputs: no float32 observation with RW_OBS_PACKED (pass obs = NULL and read RW_BUF_OBS_PACKED)");
     RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
     const struct { void *dst; int kind; } parts[] = {{obs, RW_BUF_OBS}, {rewards, RW_BUF_REWARDS}, {terminated, RW_BUF_TERMINATED},
                                                      {features, RW_BUF_FEATURES}};
@@ -1385,6 +1509,8 @@ int rw_write(rw_engine *eng, int kind, const void *host_src, size_t bytes) {
         return fail(eng, RW_ERR_INVALID_ARG, "rw_write kind %d: %zu bytes given, buffer holds %zu", kind, bytes, eng->buf[kind].bytes);
     // engine-owned flags: the step kernel stores them only when they change (truncated never does, :942), so a host write
     // would stick for the engine's lifetime — refused rather than silently different from the reference
+    if (kind == RW_BUF_OBS_PACKED)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_write: RW_BUF_OBS_PACKED is read-only (an output of the step kernels)");
     if (kind == RW_BUF_TRUNCATED)
         return fail(eng, RW_ERR_INVALID_ARG, "rw_write: RW_BUF_TRUNCATED is read-only (the reference never truncates, rware/warehouse.py:942)");
     RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
@@ -1448,6 +1574,7 @@ int rw_get_info(const rw_engine *eng, rw_info *out) {
     out->pipe_envs_per_workgroup = eng->pipe.E;
     out->pipe_workgroups = eng->pipe.grid;
     out->stats = eng->stats ? 1 : 0;
+    out->obs_packed = eng->packed ? 1 : 0;
     out->wave_priority = (eng->step.prio ? 1 : 0) | (eng->rollout.prio ? 2 : 0);
     out->specialised = eng->build_kind != 0 ? 1 : 0;
     out->build_kind = eng->build_kind;
@@ -1462,7 +1589,7 @@ int rw_get_info(const rw_engine *eng, rw_info *out) {
     // (read + write); IMAGE_DICT: the feature vectors.  The physical (PMC) traffic of a step is checked against this figure
     // (profiles/tools/sweep_collect.py), and bench.py's `frac_engine` is priced on it: a fraction of a bandwidth, never above 1.
     out->engine_bytes_per_env_step =
-        (int64_t)p.HW * (eng->wide ? 2 : 1) + 8LL * p.N + 4LL * p.N * (1 + eng->msg_bits) + 4LL * p.Q + 16 + 4LL * p.N * eng->L +
+        (int64_t)p.HW * (eng->wide ? 2 : 1) + 8LL * p.N + 4LL * p.N * (1 + eng->msg_bits) + 4LL * p.Q + 16 + 4LL * p.N * eng->row_words +
         4LL * p.N + 1 + (eng->msg_bits ? 8LL * p.N : 0) + (p.features ? 24LL * p.N : 0);
     snprintf(out->device_name, sizeof out->device_name, "%s", eng->prop.name);
     snprintf(out->arch_name, sizeof out->arch_name, "%s", eng->prop.gcnArchName);

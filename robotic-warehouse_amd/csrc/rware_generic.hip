@@ -7,6 +7,10 @@
 #ifndef RW_STATS_BUILD
 #define RW_STATS_BUILD 1
 #endif
+// ... and the packed observation rows (RW_OBS_PACKED), by the same route
+#ifndef RW_PACKED_BUILD
+#define RW_PACKED_BUILD 1
+#endif
 #include "rware_kernel_table.h"
 
 #ifndef RW_GENERIC_R
@@ -36,6 +40,7 @@ step_kernel_t RW_CAT(generic_r, RW_GENERIC_R)(bool rollout, bool wide, bool imag
 
 #if RW_GENERIC_R == 1
 bool generic_has_stats() { return RW_STATS_BUILD != 0; }
+bool generic_has_packed() { return RW_PACKED_BUILD != 0; }
 #endif
 
 }  // namespace rw_tab

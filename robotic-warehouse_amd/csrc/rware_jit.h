@@ -24,6 +24,7 @@ struct Shape {
     int directional;                 // IMAGE: image_observation_directional (else -1)
     int nt;                          // per-step kernel: 1 = non-temporal observation stores
     int stats;                       // 1: compiled with RW_STATS_BUILD — the event counters of RW_STATS_ON (rware_kernels.h)
+    int packed;                      // 1: compiled with RW_PACKED_BUILD — a build for an RW_OBS_PACKED engine: packed rows only, no float expansion
 };
 
 struct Result {

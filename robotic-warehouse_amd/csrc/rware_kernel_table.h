@@ -18,5 +18,8 @@ step_kernel_t generic_r5(bool rollout, bool wide, bool image, bool msg);
 // The library's own build: generic yes, specialised no (the host-thread emulation build of the tests: both).
 bool generic_has_stats();
 bool static_has_stats();
+// ... and with the packed observation rows (RW_PACKED_BUILD)?  The library's own build: generic yes; the ahead-of-time specialised
+// kernels never carry them (their ISA is pinned: tests/golden/isa).
+bool generic_has_packed();
 
 }  // namespace rw_tab

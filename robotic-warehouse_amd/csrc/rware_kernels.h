@@ -75,8 +75,36 @@
 #ifndef RW_STATS_BUILD
 #define RW_STATS_BUILD 0
 #endif
+// RW_PACKED_BUILD: the bit-packed observation rows of RW_OBS_PACKED (rware_phase_expand_packed.h) are compiled in — the generic kernels
+// (rware_generic.hip) and the run-time builds rw_create asks for when the caller wants packed rows (rware_jit.h).  0: nothing of it exists.
+#ifndef RW_PACKED_BUILD
+#define RW_PACKED_BUILD 0
+#endif
 
 namespace rw {
+
+// The three primitives of the packed observation rows (RW_PACKED_BUILD, rware_phase_expand_packed.h) and of rw_unpack_obs.  They live here,
+// with a plain-C++ form beside the gfx950 one, so that a host build of these sources needs nothing beyond what rware_cdna4.h already gives it.
+//   u32x4 / store_u4 / store_u4_nt   a 16-byte store of four dwords (global_store_dwordx4), cached or with the non-temporal hint
+//   funnel_shr(lo, hi, sh)           bits [sh, sh + 32) of the 64-bit value hi:lo, sh taken mod 32 (v_alignbit_b32)
+struct alignas(16) u32x4 { uint32_t x, y, z, w; };
+#if defined(__HIPCC__) || defined(__HIPCC_RTC__)
+__device__ __forceinline__ void store_u4(u32x4 *dst, u32x4 v) {
+    typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
+    u4_t vv = {v.x, v.y, v.z, v.w};
+    *reinterpret_cast<u4_t *>(dst) = vv;
+}
+__device__ __forceinline__ void store_u4_nt(u32x4 *dst, u32x4 v) {
+    typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
+    u4_t vv = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(vv, reinterpret_cast<u4_t *>(dst));
+}
+__device__ __forceinline__ uint32_t funnel_shr(uint32_t lo, uint32_t hi, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }
+#else
+inline void store_u4(u32x4 *dst, u32x4 v) { *dst = v; }
+inline void store_u4_nt(u32x4 *dst, u32x4 v) { *dst = v; }  // (the hint has no host meaning)
+inline uint32_t funnel_shr(uint32_t lo, uint32_t hi, uint32_t sh) { return (uint32_t)((((uint64_t)hi << 32) | lo) >> (sh & 31u)); }
+#endif
 
 // (the two type-level helpers the kernel needs, spelled out: the run-time compiler — hipRTC, rware_jit.cpp — has no <type_traits>)
 template <bool C, typename A, typename B> struct pick_type { using type = A; };
@@ -158,7 +186,7 @@ struct LaunchArgs {
     // fused rollout (rw_step_many_device): n_steps consecutive steps in ONE launch; the env chunk stays
     // in LDS between steps, only actions are read and obs/rewards/terminated written per step.
     int32_t n_steps;
-    float *obs;                 // [B][N][L]
+    float *obs;                 // [B][N][L]; OP_FLAG_PACKED: uint32 [B][N][PW] through the same slot (obs_stride in words)
     float *rewards;             // [B][N]
     uint8_t *terminated;        // [B]
     const uint8_t *reset_mask;  // [B]                                                  (OP_RESET)
@@ -182,7 +210,8 @@ struct LaunchArgs {
         (la).timeline, (la).act_stride, (la).obs_stride, (la).rew_stride, (la).term_stride
 enum : int { OP_FLAG_TIMELINE = 0x100,
              OP_FLAG_STATS = 0x200,    // count deliveries / failed moves into Params::stat_* (see count_events, rware_phase_goals.h)
-             OP_FLAG_PRIO = 0x400 };   // raise the wavefronts' priority until the agent phases are done (see the kernel's prologue)
+             OP_FLAG_PRIO = 0x400,     // raise the wavefronts' priority until the agent phases are done (see the kernel's prologue)
+             OP_FLAG_PACKED = 0x800 }; // `obs` is uint32 [B][N][PW]: store the observation bit string as bits (RW_PACKED_BUILD kernels only)
 enum : int { TL_START = 0, TL_ZEROED, TL_DMA_ISSUED, TL_ENV_LOADED, TL_LOADED, TL_AGENTS, TL_RESET, TL_OBS_BITS,
              TL_OBS_STORED, TL_END,  // 10, 11: where the wavefronts ran
              TL_AG_RECORD = 12, TL_AG_CELLS, TL_AG_WINNERS, TL_AG_APPLIED, TL_AG_GOALS,  // inside the agent phases (wavefront 0)
@@ -467,6 +496,17 @@ rware_step_kernel(const Params *__restrict__ cp, RW_LAUNCH_PARAMS) {
 #else
     constexpr bool stats_on = false;
 #endif
+    // Packed observation rows (RW_OBS_PACKED): like the counters, the code exists only where RW_PACKED_BUILD is set.  A generic kernel carries
+    // both expansions and takes one by the (preloaded, workgroup-uniform) flag; a run-time build is made for ONE engine, so a packed one
+    // has the float expansion compiled out.
+#if RW_PACKED_BUILD
+#ifdef __HIPCC_RTC__
+    constexpr bool kPackedOnly = true;
+#else
+    constexpr bool kPackedOnly = false;
+#endif
+    const bool packed_on = !kImage && (kPackedOnly || (la.op & OP_FLAG_PACKED) != 0);
+#endif
     // Start stagger (launches of two or more rounds of workgroups; rw_create decides, bits 16.. of `op`): the workgroups of a launch
     // start together and stay in lock-step — all stage in, all run their agent phases, all store — so the memory system and the
     // SIMDs take turns idling, and the second round inherits the rhythm.  The k-th of the first eight workgroups a CU receives
@@ -730,7 +770,14 @@ rware_step_kernel(const Params *__restrict__ cp, RW_LAUNCH_PARAMS) {
         RW_PIPE_MARK(6, 3);
     }
 
+#if RW_PACKED_BUILD
+#include "rware_phase_expand_packed.h"
+    if (!packed_on) {
+#endif
 #include "rware_phase_expand.h"
+#if RW_PACKED_BUILD
+    }
+#endif
     RW_MARK(TL_OBS_STORED);
     RW_PIPE_MARK(5, 1);
     if (!split && kRollout) write_back(wave, nw);

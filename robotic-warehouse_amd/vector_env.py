@@ -7,6 +7,8 @@ plus `num_envs`, and exposes the Gymnasium VectorEnv surface:
     obs, rewards, terminated, truncated, info   = env.step(actions)
 
 with obs float32 (B, N, L), rewards float32 (B, N), terminated/truncated bool (B,), info {}.
+`obs_format="packed"` (opt-in, FLATTENED only): obs is uint32 (B, N, PW) instead — the same observation as bits, 16 bytes per agent
+at sensor_range 1 — and `env.unpack_obs(obs)` gives the float32 form back bit for bit (packing.py has the format).
 `obs[:, i, :]` is agent i's FLATTENED observation, i.e. element i of the reference's obs tuple
 (:944); `terminated` is the reference's `done` (:935-941); `truncated` is always False (:942).
 
@@ -22,6 +24,7 @@ import numpy as np
 from . import _capi
 from .enums import DEFAULT_IMAGE_LAYERS, Action, ImageLayer, ObservationType, RewardType, enum_value
 from .layout import Layout, layout_from_params, layout_from_str, obs_length
+from .packing import packed_words, unpack_obs as _unpack_obs
 
 try:  # gymnasium is optional (absent in the build image); subclass VectorEnv when present
     import gymnasium as _gym
@@ -147,7 +150,10 @@ class WarehouseVecEnv(_VectorEnvBase):
                  normalised_coordinates: bool = False, render_mode=None, *,
                  autoreset_mode: str = "next_step", devices=None, output: str = "numpy",
                  envs_per_workgroup: int = 0, threads_per_workgroup: int = 0, library: str | None = None,
-                 obs_stores: str | None = None, jit=None, pipe=None, stats: bool = False, wave_priority=None):
+                 obs_stores: str | None = None, jit=None, pipe=None, stats: bool = False, wave_priority=None,
+                 obs_format: str = "float32"):
+        if obs_format not in ("float32", "packed"):
+            raise ValueError('obs_format must be "float32" or "packed"')
         if not 0 <= int(msg_bits) <= 16:
             raise ValueError("msg_bits must be in 0..16")
         self.msg_bits = int(msg_bits)
@@ -155,6 +161,12 @@ class WarehouseVecEnv(_VectorEnvBase):
         # DICT (rware/warehouse.py:676-720): the engine produces the FLATTENED vector — spaces.flatten() of exactly that
         # nested dict (:432-443, :505-522) — and the host hands out the batched dict as views / casts of it.
         self._dict_obs = self.observation_type == ObservationType.DICT
+        # "packed": the engine writes uint32 (B, N, PW) rows — the FLATTENED observation as bits (RW_OBS_PACKED) — and keeps no float32
+        # observation buffer at all; reset() / step() / rollout() / capture_loop hand those rows out, unpack_obs() expands them
+        self.obs_format = obs_format
+        self._packed = obs_format == "packed"
+        if self._packed and self._dict_obs:
+            raise ValueError('obs_format="packed" is the FLATTENED vector as bits: use observation_type=FLATTENED (dict_from_flat takes unpacked input)')
         engine_obs_type = ObservationType.FLATTENED if self._dict_obs else self.observation_type
         layers = tuple(ImageLayer(enum_value(l)) for l in (image_observation_layers or DEFAULT_IMAGE_LAYERS))
         # AGENT_DIRECTION / AGENT_LOAD are written with transposed indices by the reference (rware/warehouse.py:552,558):
@@ -234,7 +246,9 @@ class WarehouseVecEnv(_VectorEnvBase):
                 stats=stats,
                 # None / "auto": the engine's measured rule (rw_info.wave_priority); False / True: the launches never / always run the chain
                 # in front of their first observation store at raised wavefront priority (RW_PRIO_OFF / RW_PRIO_ON) — a scheduling hint
-                wave_priority=wave_priority))
+                wave_priority=wave_priority,
+                # obs_format="packed": RW_OBS_PACKED (the engine refuses the IMAGE types with it)
+                obs_packed=self._packed))
         self._bounds = [b for b in self._bounds if b[1] > b[0]]
         self.shard_bounds = list(self._bounds)  # env range [lo, hi) of every engine / device, in order
         self.devices = devices[: len(self.engines)]
@@ -261,19 +275,31 @@ class WarehouseVecEnv(_VectorEnvBase):
             self.observation_space = _Space((b, n) + shape, np.float32)
             self.action_space = _Space((b, n), np.int64, n=len(Action))
             return
+        # the observation spaces: float32 (L,) per agent, or — obs_format="packed" — uint32 rows of PW words per agent (packing.py);
+        # the action spaces are the same for both
+        pw = self.packed_words = packed_words(self.sensor_range, self.msg_bits) if self._packed else 0
         if _gym is not None:
             sp = _gym.spaces
-            sa_obs = sp.Box(low=-float("inf"), high=float("inf"), shape=(l,), dtype=np.float32)
-            self.single_observation_space = sp.Tuple(tuple(n * [sa_obs]))      # rware/warehouse.py:505-522
+            if self._packed:
+                hi = np.iinfo(np.uint32).max
+                self.single_observation_space = sp.Box(low=0, high=hi, shape=(n, pw), dtype=np.uint32)
+                self.observation_space = sp.Box(low=0, high=hi, shape=(b, n, pw), dtype=np.uint32)
+            else:
+                sa_obs = sp.Box(low=-float("inf"), high=float("inf"), shape=(l,), dtype=np.float32)
+                self.single_observation_space = sp.Tuple(tuple(n * [sa_obs]))      # rware/warehouse.py:505-522
+                self.observation_space = sp.Box(-float("inf"), float("inf"), shape=(b, n, l), dtype=np.float32)
             sa_act = sp.Discrete(len(Action)) if not self.msg_bits else sp.MultiDiscrete([len(Action)] + self.msg_bits * [2])
             self.single_action_space = sp.Tuple(tuple(n * [sa_act]))  # :255-260
-            self.observation_space = sp.Box(-float("inf"), float("inf"), shape=(b, n, l), dtype=np.float32)
             nvec = np.full((b, n), len(Action)) if not self.msg_bits else np.tile([len(Action)] + self.msg_bits * [2], (b, n, 1))
             self.action_space = sp.MultiDiscrete(nvec)
         else:
-            self.single_observation_space = tuple(_Space((l,), np.float32) for _ in range(n))
+            if self._packed:
+                self.single_observation_space = _Space((n, pw), np.uint32)
+                self.observation_space = _Space((b, n, pw), np.uint32)
+            else:
+                self.single_observation_space = tuple(_Space((l,), np.float32) for _ in range(n))
+                self.observation_space = _Space((b, n, l), np.float32)
             self.single_action_space = tuple(_Space((), np.int64, n=len(Action)) for _ in range(n))
-            self.observation_space = _Space((b, n, l), np.float32)
             self.action_space = _Space((b, n), np.int64, n=len(Action))
 
     # ------------------------------------------------------------------------------- hot path
@@ -452,7 +478,8 @@ class WarehouseVecEnv(_VectorEnvBase):
         if actions.dtype != t.int32 or not actions.is_contiguous():
             actions = actions.to(t.int32).contiguous()
         dev = actions.device
-        obs = t.empty((T,) + tuple(eng.shapes["obs"]), dtype=t.float32, device=dev) if want_obs else None
+        # (packed: the uint32 rows as an int32 tensor — same bits; torch's uint32 has no shift ops — unpack_obs takes it as is)
+        obs = t.empty((T,) + tuple(eng.shapes[eng.obs_name]), dtype=t.int32 if self._packed else t.float32, device=dev) if want_obs else None
         rew = t.empty((T, self.num_envs, self.n_agents), dtype=t.float32, device=dev)
         term = t.empty((T, self.num_envs), dtype=t.uint8, device=dev)
         self._live_actions = actions
@@ -552,7 +579,7 @@ class WarehouseVecEnv(_VectorEnvBase):
             return self._obs_of(self._torch_views())
         if self._index_layers:
             self.sync()  # IndexError where the reference's _make_img_obs raises it (device tensors: at sync())
-        obs = self._gather("obs")
+        obs = self._gather("obs_packed" if self._packed else "obs")
         if self._dict_obs:
             return self.dict_from_flat(obs)
         if self.observation_type == ObservationType.IMAGE_DICT:
@@ -563,7 +590,10 @@ class WarehouseVecEnv(_VectorEnvBase):
         """The DICT observation (rware/warehouse.py:676-720) of every agent, batched: same nesting and keys as the
         reference's per-agent dict, every leaf an array with leading (B, N) — `location` (B,N,2) int32, the
         MultiBinary(1) fields (B,N,1), `direction` (B,N), `local_message` (B,N,M) or None, `sensors` a tuple of
-        (2r+1)^2 dicts in the reference's row-major window order.  `flat` is the FLATTENED batch (B, N, L)."""
+        (2r+1)^2 dicts in the reference's row-major window order.  `flat` is the FLATTENED batch (B, N, L) — float32, i.e. UNPACKED:
+        with obs_format="packed" pass `env.unpack_obs(obs)`."""
+        if np.asarray(flat).shape[-1] != self.obs_length:
+            raise ValueError(f"dict_from_flat takes the float32 FLATTENED batch (..., {self.obs_length}); unpack packed rows with unpack_obs() first")
         M, cells = self.msg_bits, (2 * self.sensor_range + 1) ** 2
         i8 = lambda a: a.astype(np.int64)
         out = {"self": {
@@ -625,7 +655,9 @@ class WarehouseVecEnv(_VectorEnvBase):
         if v is None:
             t, eng, dev = self._torch, self.engines[d], self.devices[d]
             v = {k: t.as_tensor(eng.device_array(k), device=f"cuda:{dev}")
-                 for k in ("obs", "rewards", "terminated", "truncated", "features")}
+                 for k in ("rewards", "terminated", "truncated", "features")}
+            # (packed: "obs" is the uint32 (B, N, PW) buffer, held as int32 — same bits; torch's uint32 has no shift ops)
+            v["obs"] = t.as_tensor(eng.device_array("obs_packed", dtype=np.int32) if self._packed else eng.device_array("obs"), device=f"cuda:{dev}")
             v["terminated_bool"] = v["terminated"].view(t.bool)  # uint8 0/1 reinterpreted: no kernel, no copy
             v["truncated_bool"] = v["truncated"].view(t.bool)
             self._tviews[d] = v
@@ -647,10 +679,17 @@ class WarehouseVecEnv(_VectorEnvBase):
         return {k: self._gather(n) for k, n in names.items()}
 
     def device_tensor(self, name):
-        """Zero-copy torch view of any engine buffer (single-device envs)."""
+        """Zero-copy torch view of any engine buffer (single-device envs).  "obs_packed" (obs_format="packed") comes as int32 — the
+        uint32 rows' bits; "obs" does not exist with that format and raises."""
         import torch
 
-        return torch.as_tensor(self.engines[0].device_array(name), device=f"cuda:{self.devices[0]}")
+        dt = np.int32 if name == "obs_packed" else None
+        return torch.as_tensor(self.engines[0].device_array(name, dtype=dt), device=f"cuda:{self.devices[0]}")
+
+    def unpack_obs(self, packed):
+        """Packed rows (..., PW) -> float32 (..., L) with this env's parameters: bit for bit what obs_format="float32" returns.  numpy in
+        -> numpy out; a torch tensor -> a torch tensor on the same device (plain shift / and / cast ops: call it on a minibatch)."""
+        return _unpack_obs(packed, self.grid_size, self.sensor_range, self.msg_bits, self.normalised_coordinates)
 
     # ------------------------------------------------------------------------------- state
     def get_state(self) -> dict:
