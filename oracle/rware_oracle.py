@@ -10,6 +10,7 @@ product's own `layout.py`, so the two check each other).
 from __future__ import annotations
 
 import ctypes as C
+import fcntl
 import os
 import subprocess
 
@@ -24,10 +25,14 @@ def build(force: bool = False) -> str:
     alt = os.environ.get("RWARE_ORACLE_SO")  # e.g. the ASAN/UBSAN build made by oracle/sanitize.sh
     if alt:
         return alt
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(_SRC):
-        subprocess.check_call(
-            ["gcc", "-O2", "-std=c11", "-shared", "-fPIC", "-Wall", "-o", _SO, _SRC]
-        )
+    # one build at a time, moved into place when complete: pytest-xdist workers all get here at once on a fresh checkout, and a
+    # worker must never load a half-written library
+    with open(_SRC) as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(_SRC):
+            tmp = f"{_SO}.{os.getpid()}.tmp"
+            subprocess.check_call(["gcc", "-O2", "-std=c11", "-shared", "-fPIC", "-Wall", "-o", tmp, _SRC])
+            os.replace(tmp, _SO)
     return _SO
 
 

@@ -5,10 +5,12 @@
 bit-exact on every field (grid, agent SoA, queue, counters, PCG64 state, obs, rewards, done)."""
 import os
 import re
+from collections import Counter
 
 import numpy as np
 import pytest
 
+import collision_scenarios as cs
 import golden_util as gu
 from engine_backend import EngineBackend
 from rware_oracle import OracleVecEnv
@@ -905,9 +907,15 @@ def test_agent_count_static_builds_match_oracle(env_id):
 ])
 def test_crowded_warehouses_resolve_long_chains(env_id, p_forward, geom):
     """9 .. 19 agents on the 110 cells of the tiny warehouse (and the 4-env geometry on the small one) under a forward-heavy
-    policy: long follower chains, contested cells with unequal depths, blocked tails and cycles on nearly every step — the
-    per-cell agent phases of the per-step kernels and the register-exchange ones of the fused rollout (wide priority words,
-    64- / 128-bit chain links) against the oracle's literal networkx restatement, every env, every step."""
+    policy — the per-cell agent phases of the per-step kernels and the register-exchange ones of the fused rollout (wide priority words,
+    64- / 128-bit chain links) against the oracle's literal networkx restatement, every env, every step.
+
+    What that play holds, measured with collision_scenarios.analyse on the oracle's pre-step states (64 of the 256 envs x 150
+    steps, printed by the test): contested cells and refused 2-swaps on most steps, but real cycles and deep chains hardly ever —
+    cycles (>= 3 agents) / deepest chain / junctions with unequal depths / ties / 2-swaps:  tiny-9ag 0 / 2 / 13 / 198 / 1599,
+    tiny-12ag-easy 2 / 4 / 45 / 348 / 2270, tiny-13ag 1 / 4 / 57 / 391 / 2852, tiny-16ag 3 / 5 / 98 / 518 / 3798,
+    tiny-17ag-hard 5 / 4 / 121 / 632 / 3417, tiny-19ag 7 / 5 / 150 / 591 / 6041, small-16ag 0 / 3 / 51 / 432 / 3555,
+    small-19ag 4 / 4 / 87 / 548 / 4788.  The rare structures are pinned by construction in test_collision_structures.py."""
     kw = rware_amd.env_kwargs(env_id)
     kw["max_steps"] = 60
     kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
@@ -918,11 +926,17 @@ def test_crowded_warehouses_resolve_long_chains(env_id, p_forward, geom):
     assert np.array_equal(env.reset(seed=31)[0], orc.reset(seed=31))
     rng = np.random.default_rng(33)
     rest = (1.0 - p_forward) / 4
+    seen = Counter()
     for t in range(150):
         a = rng.choice(5, size=(B, N), p=[rest, p_forward, rest, rest, rest]).astype(np.int32)
+        so = orc.get_state()
+        for e in range(64):                                     # what this step is made of: the oracle's pre-step state, a quarter of the envs
+            seen.update(cs.analyse(so["agent_x"][e], so["agent_y"][e], so["agent_dir"][e], so["agent_carry"][e], a[e], orc.H, orc.W, so["grid"][e, 1])[0])
         obs, rew, term, _, _ = env.step(a)
         o2, r2, d2 = orc.step_autoreset(a, "next_step")
         assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
+    print(f"census {env_id} (64 envs x 150 steps): {dict(sorted(seen.items()))}")
+    assert seen
     acts = rng.choice(5, size=(25, B, N), p=[rest, p_forward, rest, rest, rest]).astype(np.int32)
     obs, rew, term = env.rollout(acts)                      # the fused rollout keeps the all-gather (register) agent phases
     for k in range(25):
