@@ -5,8 +5,10 @@ The gfx950 build of the same sources is checked by the -m gpu tests."""
 import numpy as np
 import pytest
 
+import engine_checks as ec
 import golden_util as gu
 from engine_backend import EngineBackend, build_emu
+from lockstep import check_rollout, lockstep, oracle_kwargs, same_obs, same_state
 from rware_oracle import OracleVecEnv
 
 import rware_amd
@@ -63,37 +65,23 @@ def test_emulated_engine_matches_reference_golden(name, geom):
     ("rware-small-4ag-v1", {"max_steps": 25, "msg_bits": 2}, 16, (0, 0)),
 ])
 def test_emulated_engine_matches_oracle(env_id, extra, B, geom, mode):
-    kw = rware_amd.env_kwargs(env_id)
-    kw.update(extra)
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
-    env = rware_amd.WarehouseVecEnv(B, autoreset_mode=mode, library=LIB, envs_per_workgroup=geom[0],
-                                    threads_per_workgroup=geom[1], **kw)
-    orc = OracleVecEnv(B, **kw)
+    kw = oracle_kwargs(env_id, **extra)
+    env, orc = ec.make_pair(B, kw, library=LIB, geom=geom, autoreset_mode=mode)
     assert env.engines[0].info.specialised == (1 if geom in ((0, 0), (16, 256)) else 0)
-    obs, _ = env.reset(seed=99)
-    assert np.array_equal(obs, orc.reset(seed=99))
     rng = np.random.default_rng(3)
     M = kw.get("msg_bits", 0)
-    for t in range(70):
+
+    def act(t):
         a = rng.choice(5, size=(B, kw["n_agents"]), p=[0.1, 0.55, 0.1, 0.1, 0.15]).astype(np.int32)
         if M:
             a = np.concatenate([a[..., None], rng.integers(0, 2, size=(B, kw["n_agents"], M), dtype=np.int32)], axis=-1)
-        obs, rew, term, trunc, info = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, mode)
-        assert np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
-        assert np.array_equal(obs, o2), t
-        if mode == "same_step":
-            # the terminal observation of the step that ended (and reset) an episode: info["final_obs"], as Gymnasium >= 1.0 has it
-            # (FLATTENED and, round 5, the IMAGE types)
-            assert ("final_obs" in info) == bool(d2.any()), t
-            if d2.any():
-                assert np.array_equal(info["_final_obs"], orc.final_mask)
-                assert np.array_equal(info["final_obs"][orc.final_mask], orc.final_obs[orc.final_mask]), t
-        else:
-            assert info == {}
-        st, so = env.get_state(), orc.get_state()
-        for k in so:
-            assert np.array_equal(st[k], so[k]), (k, t)
+        return a
+
+    def no_info(t, obs, rew, term, info):
+        assert mode == "same_step" or info == {}, t
+
+    # (same_step: the terminal observation of the step that ended (and reset) an episode, info["final_obs"], as Gymnasium >= 1.0 has it)
+    lockstep(env, orc, act, mode, seed=99, steps=70, state_every=1, on_step=no_info)
     env.close()
 
 
@@ -130,12 +118,8 @@ def test_masked_reset_and_reseed():
     B = 6
     env = rware_amd.WarehouseVecEnv(B, library=LIB, envs_per_workgroup=4, threads_per_workgroup=64, **kw)
     orc = OracleVecEnv(B, **kw)
-    env.reset(seed=5)
-    orc.reset(seed=5)
     a = np.random.default_rng(0).integers(0, 5, size=(B, 2))
-    for _ in range(5):
-        env.step(a)
-        orc.step_autoreset(a, "next_step")
+    lockstep(env, orc, lambda t: a, seed=5, steps=5)
     mask = np.array([1, 0, 0, 1, 0, 1], np.uint8)
     obs, _ = env.reset(mask=mask)                       # continue the streams of envs 0, 3, 5
     assert np.array_equal(obs, orc.reset(mask=mask))
@@ -144,9 +128,7 @@ def test_masked_reset_and_reseed():
         from rware_oracle import seed_state
         orc.rng[e] = seed_state(11 + int(e))
     assert np.array_equal(obs, orc.reset(mask=mask))
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
+    same_state(env.get_state(), orc.get_state(), "masked reset")
     env.close()
 
 
@@ -221,47 +203,25 @@ def test_sharded_env_equals_unsharded():
 ])
 def test_fused_rollout_equals_stepwise_oracle(env_id, extra, B, geom, mode):
     """rw_step_many_device (one launch, env chunk resident in LDS across steps) == T single steps."""
-    kw = rware_amd.env_kwargs(env_id)
-    kw.update(extra)
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
-    env = rware_amd.WarehouseVecEnv(B, library=LIB, autoreset_mode=mode, envs_per_workgroup=geom[0],
-                                    threads_per_workgroup=geom[1], **kw)
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=3)[0], orc.reset(seed=3))
+    kw = oracle_kwargs(env_id, **extra)
+    env, orc = ec.make_pair(B, kw, library=LIB, geom=geom, autoreset_mode=mode)
+    same_obs(env.reset(seed=3)[0], orc.reset(seed=3), "reset obs", "reset")
     T = 37
     acts = np.random.default_rng(0).choice(5, size=(T, B, kw["n_agents"]), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-    obs, rew, term = env.rollout(acts)
-    for t in range(T):
-        o2, r2, d2 = orc.step_autoreset(acts[t], mode)
-        assert np.array_equal(obs[t], o2) and np.array_equal(rew[t], r2) and np.array_equal(term[t], d2.astype(bool)), t
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
-    # and the stepwise path continues from the fused one
-    a = acts[0]
-    o, r, d, _, _ = env.step(a)
-    o2, r2, d2 = orc.step_autoreset(a, mode)
-    assert np.array_equal(o, o2) and np.array_equal(r, r2)
+    check_rollout(env, orc, acts, mode)
+    lockstep(env, orc, acts[:1], mode, seed=None, t0=T)    # and the stepwise path continues from the fused one
     env.close()
 
 
 @pytest.mark.parametrize("sensor_range", [4, 5])
 def test_wide_sensor_ranges(sensor_range):
     """r = 4 (63-bit window rows) and r = 5 (77-bit rows, the multi-word path of the row gather)."""
-    kw = rware_amd.env_kwargs("rware-tiny-3ag-v1")
-    kw.update(sensor_range=sensor_range, max_steps=12)
-    kw["reward_type"] = kw["reward_type"].value
+    kw = oracle_kwargs("rware-tiny-3ag-v1", sensor_range=sensor_range, max_steps=12)
     B = 5
-    env = rware_amd.WarehouseVecEnv(B, library=LIB, envs_per_workgroup=4, threads_per_workgroup=64, **kw)
-    orc = OracleVecEnv(B, **kw)
+    env, orc = ec.make_pair(B, kw, library=LIB, geom=(4, 64))
     assert env.obs_length == 8 + 7 * (2 * sensor_range + 1) ** 2
-    assert np.array_equal(env.reset(seed=1)[0], orc.reset(seed=1))
     rng = np.random.default_rng(2)
-    for t in range(30):
-        a = rng.integers(0, 5, size=(B, 3))
-        o, r, d, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(o, o2) and np.array_equal(r, r2), t
+    lockstep(env, orc, lambda t: rng.integers(0, 5, size=(B, 3)), seed=1, steps=30)
     env.close()
 
 
@@ -269,22 +229,11 @@ def test_wide_sensor_ranges(sensor_range):
 def test_many_agents_one_env_per_wavefront(n_agents):
     """N > 32: one env per wavefront in the agent phases (64 / N == 1), agent ids up to the 7-bit limit of the
     LDS agent layer, crowded enough that chains and cycles happen every step."""
-    kw = rware_amd.env_kwargs("rware-medium-19ag-v1")
-    kw.update(n_agents=n_agents, request_queue_size=n_agents, max_steps=25)
-    kw["reward_type"] = kw["reward_type"].value
+    kw = oracle_kwargs("rware-medium-19ag-v1", n_agents=n_agents, request_queue_size=n_agents, max_steps=25)
     B = 5
-    env = rware_amd.WarehouseVecEnv(B, library=LIB, **kw)
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=3)[0], orc.reset(seed=3))
+    env, orc = ec.make_pair(B, kw, library=LIB)
     rng = np.random.default_rng(8)
-    for t in range(60):
-        a = rng.choice(5, size=(B, n_agents), p=[.05, .65, .1, .1, .1])
-        o, r, d, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(o, o2) and np.array_equal(r, r2) and np.array_equal(d, d2.astype(bool)), t
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
+    lockstep(env, orc, lambda t: rng.choice(5, size=(B, n_agents), p=[.05, .65, .1, .1, .1]), seed=3, steps=60)
     env.close()
 
 
@@ -293,19 +242,10 @@ def test_wide_shelf_ids_use_the_uint16_shadow():
     kw = dict(shelf_columns=9, column_height=8, shelf_rows=3, n_agents=10, sensor_range=1, request_queue_size=5,
               max_inactivity_steps=None, max_steps=14, reward_type=0)
     B = 4
-    env = rware_amd.WarehouseVecEnv(B, library=LIB, envs_per_workgroup=4, threads_per_workgroup=128, **kw)
+    env, orc = ec.make_pair(B, kw, library=LIB, geom=(4, 128))
     assert env.n_shelves > 255
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=8)[0], orc.reset(seed=8))
     rng = np.random.default_rng(5)
-    for t in range(35):
-        a = rng.choice(5, size=(B, 10), p=[.1, .5, .1, .1, .2])
-        o, r, d, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(o, o2) and np.array_equal(r, r2) and np.array_equal(d, d2.astype(bool)), t
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
+    lockstep(env, orc, lambda t: rng.choice(5, size=(B, 10), p=[.1, .5, .1, .1, .2]), seed=8, steps=35)
     env.close()
 
 
@@ -341,35 +281,9 @@ def test_snapshot_restore_replays_bit_identically():
     (3, True, [2, 1], 3),              # IMAGE_DICT with two layers
 ])
 def test_image_observations_match_oracle(obs_type, directional, layers, sr):
-    kw = rware_amd.env_kwargs("rware-small-5ag-v1")
-    kw.update(sensor_range=sr, max_steps=16)
-    kw["reward_type"] = kw["reward_type"].value
-    extra = dict(observation_type=obs_type, image_observation_directional=directional, image_observation_layers=layers)
-    B = 6
-    env = rware_amd.WarehouseVecEnv(B, library=LIB, envs_per_workgroup=4, threads_per_workgroup=128, **kw, **extra)
-    orc = OracleVecEnv(B, **kw, **extra)
-
-    def same(a, b):
-        if isinstance(a, dict):
-            return np.array_equal(a["image"], b[0]) and np.array_equal(a["features"], b[1])
-        return np.array_equal(a, b)
-
-    assert same(env.reset(seed=4)[0], orc.reset(seed=4))
-    rng = np.random.default_rng(7)
-    acts = rng.choice(5, size=(40, B, 5), p=[.1, .5, .15, .15, .1])
-    for t in range(25):
-        o, r, d, _, _ = env.step(acts[t])
-        o2, r2, d2 = orc.step_autoreset(acts[t], "next_step")
-        assert same(o, o2) and np.array_equal(r, r2), t
-    img, rew, term = env.rollout(acts[25:])      # fused rollout writes the image tape
-    for t in range(25, 40):
-        o2, r2, d2 = orc.step_autoreset(acts[t], "next_step")
-        assert np.array_equal(img[t - 25], o2[0] if isinstance(o2, tuple) else o2) and np.array_equal(rew[t - 25], r2), t
-    env.close()
-
-
-SQUARE = dict(shelf_columns=3, column_height=3, shelf_rows=2, n_agents=5, msg_bits=0, sensor_range=2,
-              request_queue_size=3, max_inactivity_steps=None, max_steps=30, reward_type=1)   # a 10 x 10 grid
+    kw = oracle_kwargs("rware-small-5ag-v1", sensor_range=sr, max_steps=16, observation_type=obs_type,
+                       image_observation_directional=directional, image_observation_layers=layers)
+    ec.image_observations(kw, 6, tape_steps=40, n_step=25, library=LIB, geom=(4, 128))
 
 
 @pytest.mark.parametrize("obs_type,directional,layers", [
@@ -380,88 +294,24 @@ def test_transposed_image_layers_match_oracle(obs_type, directional, layers):
     """AGENT_DIRECTION / AGENT_LOAD as the reference writes them, layer[ag.x, ag.y] (:552, :558); on a square
     grid the transposed index is always in bounds."""
     extra = dict(observation_type=obs_type, image_observation_directional=directional, image_observation_layers=layers)
-    B = 6
-    env = rware_amd.WarehouseVecEnv(B, library=LIB, envs_per_workgroup=4, threads_per_workgroup=128, **SQUARE, **extra)
-    assert tuple(env.grid_size) == (10, 10)
-    orc = OracleVecEnv(B, **SQUARE, **extra)
-
-    def same(a, b):
-        if isinstance(a, dict):
-            return np.array_equal(a["image"], b[0]) and np.array_equal(a["features"], b[1])
-        return np.array_equal(a, b)
-
-    assert same(env.reset(seed=11)[0], orc.reset(seed=11))
-    rng = np.random.default_rng(3)
-    acts = rng.choice(5, size=(70, B, 5), p=[.1, .45, .15, .15, .15])
-    seen_dir = seen_load = 0
-    for t in range(50):
-        o, r, d, _, _ = env.step(acts[t])
-        o2, r2, d2 = orc.step_autoreset(acts[t], "next_step")
-        assert same(o, o2) and np.array_equal(r, r2), t
-        img = o["image"] if isinstance(o, dict) else o
-        seen_dir += int((img[:, :, layers.index(3)] > 1).sum())
-        seen_load += int(img[:, :, layers.index(4)].sum())
-    assert seen_dir > 0 and seen_load > 0          # the layers were exercised (values 2..4, loaded agents in view)
-    img, rew, term = env.rollout(acts[50:])
-    for t in range(50, 70):
-        o2, r2, d2 = orc.step_autoreset(acts[t], "next_step")
-        assert np.array_equal(img[t - 50], o2[0] if isinstance(o2, tuple) else o2) and np.array_equal(rew[t - 50], r2), t
-    env.close()
+    ec.transposed_image_layers(extra, layers, 6, max_steps=30, seed=11, rng_seed=3, tape_steps=70, n_step=50, library=LIB, geom=(4, 128))
 
 
 @pytest.mark.parametrize("layer", [3, 4])
 def test_transposed_image_layers_raise_indexerror_like_the_reference(layer):
     """On every registered layout H > W, so the reference's layer[ag.x, ag.y] raises IndexError once an agent
     (a loaded one for AGENT_LOAD) reaches y >= W; the engine reports it at the same step."""
-    kw = rware_amd.env_kwargs("rware-tiny-2ag-v1")
-    kw["reward_type"] = kw["reward_type"].value
-    extra = dict(observation_type=2, image_observation_layers=[2, layer])
-    B = 4
-    env = rware_amd.WarehouseVecEnv(B, library=LIB, envs_per_workgroup=4, threads_per_workgroup=64, **kw, **extra)
-    orc = OracleVecEnv(B, **kw, **extra)
-    rng = np.random.default_rng(1)
-
-    def attempt(f):
-        try:
-            return f(), False
-        except IndexError:
-            return None, True
-
-    (o, e1), (o2, e2) = attempt(lambda: env.reset(seed=2)[0]), attempt(lambda: orc.reset(seed=2))
-    assert e1 == e2
-    t = 0
-    while not e1 and t < 400:
-        a = rng.choice(5, size=(B, 2), p=[.05, .5, .15, .15, .15])
-        (res, e1), (res2, e2) = attempt(lambda: env.step(a)), attempt(lambda: orc.step_autoreset(a, "next_step"))
-        assert e1 == e2, t
-        if not e1:
-            assert np.array_equal(res[0], res2[0]), t
-        t += 1
-    assert e1, "no agent ever reached y >= W"
-    env.close()
+    ec.transposed_layers_raise_indexerror("rware-tiny-2ag-v1", layer, 4, limit=400, library=LIB, geom=(4, 64))
 
 
 def test_communication_bits_rollout_and_state():
-    kw = rware_amd.env_kwargs("rware-small-6ag-v1")
-    kw.update(msg_bits=2, max_steps=14)
-    kw["reward_type"] = kw["reward_type"].value
+    kw = oracle_kwargs("rware-small-6ag-v1", msg_bits=2, max_steps=14)
     B = 5
-    env = rware_amd.WarehouseVecEnv(B, library=LIB, envs_per_workgroup=4, threads_per_workgroup=128, autoreset_mode="same_step", **kw)
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=2)[0], orc.reset(seed=2))
+    env, orc = ec.make_pair(B, kw, library=LIB, geom=(4, 128), autoreset_mode="same_step")
     rng = np.random.default_rng(8)
     acts = np.concatenate([rng.choice(5, size=(40, B, 6, 1), p=[.1, .5, .15, .15, .1]), rng.integers(0, 2, size=(40, B, 6, 2))], axis=-1)
-    for t in range(15):
-        o, r, d, _, _ = env.step(acts[t])
-        o2, r2, d2 = orc.step_autoreset(acts[t], "same_step")
-        assert np.array_equal(o, o2) and np.array_equal(r, r2) and np.array_equal(d, d2.astype(bool)), t
-    obs, rew, term = env.rollout(acts[15:])
-    for t in range(15, 40):
-        o2, r2, d2 = orc.step_autoreset(acts[t], "same_step")
-        assert np.array_equal(obs[t - 15], o2) and np.array_equal(rew[t - 15], r2), t
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
+    lockstep(env, orc, acts[:15], "same_step", seed=2)
+    check_rollout(env, orc, acts[15:], "same_step", t0=15)
     env.close()
 
 
@@ -516,19 +366,14 @@ def test_grid_is_a_derived_view_refreshed_on_demand():
     assert np.array_equal(view, orc.get_state()["grid"])          # current when handed out
     rng = np.random.default_rng(0)
     before = view.copy()
-    for t in range(12):
-        a = rng.choice(5, size=(B, 2), p=[0.1, 0.6, 0.1, 0.1, 0.1]).astype(np.int32)
-        env.step(a)
-        orc.step_autoreset(a, "next_step")
+    # (no state comparison inside: get_state() is one of the reads that refresh the exported grid)
+    lockstep(env, orc, lambda t: rng.choice(5, size=(B, 2), p=[0.1, 0.6, 0.1, 0.1, 0.1]).astype(np.int32), seed=None, steps=12, skip=("state",))
     want = orc.get_state()["grid"]
     assert not np.array_equal(want, before), "nothing moved: the test needs a different seed"
     assert np.array_equal(view, before)                            # the steps did not touch the exported grid
     env.refresh_grid()
     assert np.array_equal(view, want)                              # ... rw_refresh_grid brings it up to date
-    a = rng.integers(0, 5, size=(B, 2), dtype=np.int32)
-    env.step(a)
-    orc.step_autoreset(a, "next_step")
-    assert np.array_equal(env.get_state()["grid"], orc.get_state()["grid"])   # get_state() is always current
+    lockstep(env, orc, lambda t: rng.integers(0, 5, size=(B, 2), dtype=np.int32), seed=None, steps=1, t0=12)   # get_state() is always current
     env.close()
 
 
@@ -558,18 +403,11 @@ def test_layouts_wider_than_256_cells_keep_exact_coordinates():
     kw = dict(shelf_columns=89, column_height=1, shelf_rows=1, n_agents=8, msg_bits=0, sensor_range=1, request_queue_size=4,
               max_inactivity_steps=None, max_steps=500, reward_type=1)
     B = 6
-    env = rware_amd.WarehouseVecEnv(B, library=LIB, envs_per_workgroup=4, threads_per_workgroup=64, **kw)
+    env, orc = ec.make_pair(B, kw, library=LIB, geom=(4, 64))
     assert env.grid_size[1] > 256
-    orc = OracleVecEnv(B, **kw)
-    obs, _ = env.reset(seed=21)
-    assert np.array_equal(obs, orc.reset(seed=21))
-    assert (obs[..., 0] >= 256).any(), "no agent beyond x = 255: pick another seed"
     rng = np.random.default_rng(2)
-    for t in range(8):
-        a = rng.choice(5, size=(B, 8), p=[0.1, 0.6, 0.1, 0.1, 0.1]).astype(np.int32)
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(obs, o2), t
+    assert (orc.reset(seed=21)[..., 0] >= 256).any(), "no agent beyond x = 255: pick another seed"
+    lockstep(env, orc, lambda t: rng.choice(5, size=(B, 8), p=[0.1, 0.6, 0.1, 0.1, 0.1]).astype(np.int32), seed=21, steps=8)
     env.close()
 
 
@@ -604,24 +442,13 @@ def test_coordinate_writes_mark_the_derived_grid_stale_and_truncated_is_read_onl
 def test_paper_task_grid_runs_exact_shape_builds(env_id):
     """tiny / small / medium x 2, 4, 6, 8 agents x easy / normal / hard each have an exact-shape build (rware_static_table.h):
     a sample of them against the oracle across an autoreset (N = 8: exact-shape build with the LDS exchange)."""
-    kw = rware_amd.env_kwargs(env_id)
-    kw["max_steps"] = 18
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
+    kw = oracle_kwargs(env_id, max_steps=18)
     B = 16
-    env = rware_amd.WarehouseVecEnv(B, library=LIB, **kw)
+    env, orc = ec.make_pair(B, kw, library=LIB)
     # (6 and 8 agents: the half-size-workgroup build serves batches up to 16384 envs)
     assert env.engines[0].info.specialised == 1 and env.engines[0].info.envs_per_workgroup == (8 if kw["n_agents"] >= 6 else 16)
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=4)[0], orc.reset(seed=4))
     rng = np.random.default_rng(6)
-    for t in range(30):
-        a = rng.choice(5, size=(B, kw["n_agents"]), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
+    lockstep(env, orc, lambda t: rng.choice(5, size=(B, kw["n_agents"]), p=[.1, .55, .1, .1, .15]).astype(np.int32), seed=4, steps=30)
     env.close()
 
 
@@ -643,10 +470,8 @@ def test_agent_arrays_are_derived_views_of_the_packed_records():
     assert np.array_equal(view, orc.get_state()["agent_x"])
     rng = np.random.default_rng(0)
     before = view.copy()
-    for t in range(12):
-        a = rng.choice(5, size=(B, 2), p=[0.1, 0.6, 0.1, 0.1, 0.1]).astype(np.int32)
-        env.step(a)
-        orc.step_autoreset(a, "next_step")
+    # (no state comparison inside: get_state() is one of the reads that refresh the exported arrays)
+    lockstep(env, orc, lambda t: rng.choice(5, size=(B, 2), p=[0.1, 0.6, 0.1, 0.1, 0.1]).astype(np.int32), seed=None, steps=12, skip=("state",))
     so = orc.get_state()
     assert not np.array_equal(so["agent_x"], before), "nothing moved: the test needs a different seed"
     assert np.array_equal(view, before)                            # the steps did not touch the exported array
@@ -661,20 +486,14 @@ def test_agent_arrays_are_derived_views_of_the_packed_records():
     for k in ("agent_x", "agent_y", "agent_carry", "agent_delivered"):
         assert np.array_equal(st2[k], st[k]), k
     assert np.array_equal(st2["agent_dir"], new_dir)
-    for t in range(6):
-        a = rng.integers(0, 5, size=(B, 2), dtype=np.int32)
-        obs, _, _, _, _ = env.step(a)
-        o2, _, _ = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(obs, o2), t
+    lockstep(env, orc, lambda t: rng.integers(0, 5, size=(B, 2), dtype=np.int32), seed=None, steps=6, t0=12)
     env.close()
 
 
 def test_two_agent_tasks_take_double_size_workgroups_from_16384_envs():
     """2 agents: the 32-env build (64 agents = one full agent wavefront) from 16384 envs up, the 16-env build below and for
     batches that are no multiple of 32; pinned here through the explicit geometry and checked against the oracle."""
-    kw = rware_amd.env_kwargs("rware-small-2ag-hard-v1")
-    kw["max_steps"] = 15
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
+    kw = oracle_kwargs("rware-small-2ag-hard-v1", max_steps=15)
     B = 64
     env = rware_amd.WarehouseVecEnv(B, library=LIB, envs_per_workgroup=32, threads_per_workgroup=256, **kw)
     assert env.engines[0].info.specialised == 1 and env.engines[0].info.envs_per_workgroup == 32
@@ -682,18 +501,10 @@ def test_two_agent_tasks_take_double_size_workgroups_from_16384_envs():
     assert small.engines[0].info.envs_per_workgroup == 16          # default geometry below 16384 envs
     small.close()
     orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=8)[0], orc.reset(seed=8))
     rng = np.random.default_rng(1)
-    for t in range(24):
-        a = rng.choice(5, size=(B, 2), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
+    lockstep(env, orc, lambda t: rng.choice(5, size=(B, 2), p=[.1, .55, .1, .1, .15]).astype(np.int32), seed=8, steps=24)
     acts = rng.choice(5, size=(10, B, 2), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-    obs, rew, term = env.rollout(acts)
-    for k in range(10):
-        o2, r2, d2 = orc.step_autoreset(acts[k], "next_step")
-        assert np.array_equal(obs[k], o2) and np.array_equal(rew[k], r2), k
+    check_rollout(env, orc, acts, t0=24)
     env.close()
 
 
@@ -740,10 +551,7 @@ def test_agent_count_static_builds_read_the_queue_length_at_run_time(env_id, ext
     """Tasks without an exact (N, Q) entry run the agent-count-static build of their size and agent count (Q == -1 in
     rware_static_table.h: any queue length up to 2 N, the LDS carve-up reserves 2 N slots): against the oracle across an
     autoreset, per-step launches and a fused rollout; Q = 0 (1 agent, hard) included."""
-    kw = rware_amd.env_kwargs(env_id)
-    kw.update(extra)
-    kw["max_steps"] = 18
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
+    kw = oracle_kwargs(env_id, **dict(extra, max_steps=18))
     B, N = 32, kw["n_agents"]
     env = rware_amd.WarehouseVecEnv(B, library=LIB, **kw)
     assert env.engines[0].info.specialised == 1
@@ -753,21 +561,10 @@ def test_agent_count_static_builds_read_the_queue_length_at_run_time(env_id, ext
     wide4 = 13 <= N <= 16 and "tiny" not in env_id
     assert env.engines[0].info.build_kind == 2 and env.engines[0].info.envs_per_workgroup == (16 if N <= 4 else 4 if wide4 else 8)
     orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=14)[0], orc.reset(seed=14))
     rng = np.random.default_rng(16)
-    for t in range(26):
-        a = rng.choice(5, size=(B, N), p=[.1, .5, .1, .1, .2]).astype(np.int32)
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
+    lockstep(env, orc, lambda t: rng.choice(5, size=(B, N), p=[.1, .5, .1, .1, .2]).astype(np.int32), seed=14, steps=26)
     acts = rng.choice(5, size=(12, B, N), p=[.1, .5, .1, .1, .2]).astype(np.int32)
-    obs, rew, term = env.rollout(acts)
-    for k in range(12):
-        o2, r2, d2 = orc.step_autoreset(acts[k], "next_step")
-        assert np.array_equal(obs[k], o2) and np.array_equal(rew[k], r2) and np.array_equal(term[k], d2.astype(bool)), k
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
+    check_rollout(env, orc, acts, t0=26)
     env.close()
 
 
@@ -820,28 +617,7 @@ def test_generic_kernel_matches_oracle_on_random_shapes(case):
               reward_type=int(g.integers(0, 3)), normalised_coordinates=bool(g.random() < 0.25))
     B = int(g.integers(3, 10))
     mode = ["next_step", "same_step", "disabled"][case % 3]
-    env = rware_amd.WarehouseVecEnv(B, library=LIB, envs_per_workgroup=4, threads_per_workgroup=int(g.choice([64, 128])), autoreset_mode=mode, **kw)
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=70 + case)[0], orc.reset(seed=70 + case))
-    rng = np.random.default_rng(case)
-    for t in range(40):
-        a = rng.choice(5, size=(B, n_agents), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, mode)
-        assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), (t, kw)
-        if mode == "disabled" and term.any():
-            m = term.astype(np.uint8)
-            assert np.array_equal(env.reset(mask=m)[0], orc.reset(mask=m)), t
-    acts = rng.choice(5, size=(8, B, n_agents), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-    if mode != "disabled":
-        obs, rew, term = env.rollout(acts)
-        for k in range(8):
-            o2, r2, d2 = orc.step_autoreset(acts[k], mode)
-            assert np.array_equal(obs[k], o2) and np.array_equal(rew[k], r2), (k, kw)
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), (k, kw)
-    env.close()
+    ec.random_shape(kw, B, mode, (4, int(g.choice([64, 128]))), case=case, seed=70 + case, n_step=40, n_roll=8, library=LIB)
 
 
 @pytest.mark.parametrize("env_id,p_forward", [
@@ -854,30 +630,7 @@ def test_crowded_warehouses_resolve_long_chains(env_id, p_forward):
     (occupant from the agent layer, winners among the target's four neighbours, pointer-chased depth and chain walk) and the
     register-exchange ones of the fused rollout (wide priority words, 128-bit chain links) against the oracle's literal networkx
     restatement."""
-    kw = rware_amd.env_kwargs(env_id)
-    kw["max_steps"] = 40
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
-    B, N = 16, kw["n_agents"]
-    env = rware_amd.WarehouseVecEnv(B, library=LIB, **kw)
-    assert env.engines[0].info.build_kind == 2 and env.engines[0].info.envs_per_workgroup == 8    # (the tiny warehouse: 8-env builds only)
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=31)[0], orc.reset(seed=31))
-    rng = np.random.default_rng(33)
-    rest = (1.0 - p_forward) / 4
-    for t in range(90):
-        a = rng.choice(5, size=(B, N), p=[rest, p_forward, rest, rest, rest]).astype(np.int32)
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
-    acts = rng.choice(5, size=(25, B, N), p=[rest, p_forward, rest, rest, rest]).astype(np.int32)
-    obs, rew, term = env.rollout(acts)                      # the fused rollout keeps the all-gather (register) agent phases
-    for k in range(25):
-        o2, r2, d2 = orc.step_autoreset(acts[k], "next_step")
-        assert np.array_equal(obs[k], o2) and np.array_equal(rew[k], r2) and np.array_equal(term[k], d2.astype(bool)), k
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
-    env.close()
+    ec.crowded_warehouse(env_id, p_forward, 16, max_steps=40, n_step=90, envs_per_workgroup=8, library=LIB)   # (the tiny warehouse: 8-env builds only)
 
 
 @pytest.mark.parametrize("threads", ["1", "0"])
@@ -916,9 +669,7 @@ def test_start_stagger_is_a_create_time_rule_and_does_not_change_results(monkeyp
     """Launches of two or more rounds of workgroups (>= 2 x 8 per CU; the emulated device has one CU) stagger the start of the first
     eight workgroups per CU (rw_info.stagger_ticks x 10 ns per slot; RWARE_STAGGER_TICKS moves the default) — where they do not run at
     raised wavefront priority (round 6: with the priority the delay is only a delay): a delay, never a different result."""
-    kw = rware_amd.env_kwargs("rware-small-4ag-v1")
-    kw["max_steps"] = 11
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
+    kw = oracle_kwargs("rware-small-4ag-v1", max_steps=11)
     prio = rware_amd.WarehouseVecEnv(256, library=LIB, **kw)             # 16 workgroups, two rounds — at raised priority: no stagger
     assert (prio.engines[0].info.wave_priority & 1, prio.engines[0].info.stagger_ticks) == (1, 0)
     prio.close()
@@ -938,13 +689,8 @@ def test_start_stagger_is_a_create_time_rule_and_does_not_change_results(monkeyp
     env = rware_amd.WarehouseVecEnv(256, library=LIB, **kw)              # 16 workgroups: two rounds
     assert env.engines[0].info.stagger_ticks == 25 and env.engines[0].info.n_workgroups == 16
     orc = OracleVecEnv(256, **kw)
-    assert np.array_equal(env.reset(seed=5)[0], orc.reset(seed=5))
     rng = np.random.default_rng(6)
-    for t in range(25):
-        a = rng.integers(0, 5, size=(256, 4), dtype=np.int32)
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
+    lockstep(env, orc, lambda t: rng.integers(0, 5, size=(256, 4), dtype=np.int32), seed=5, steps=25)
     env.close()
 
 
@@ -1032,30 +778,9 @@ def test_13_to_16_agents_step_on_4_env_workgroups_and_roll_out_on_8(monkeypatch)
     assert geom("rware-large-16ag-v1", 64) == (4, 16, 3, 0)
     monkeypatch.delenv("RWARE_WIDE_E4")
     # (9 .. 12 agents: the fused rollout follows onto the 4-env build; 13 .. 19: it stays on the 8-env one)
-    for env_id, B in (("rware-large-16ag-v1", 32), ("rware-medium-13ag-v1", 128), ("rware-small-10ag-v1", 16), ("rware-small-19ag-v1", 16)):
-        kw = rware_amd.env_kwargs(env_id)
-        kw["max_steps"] = 9
-        kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
-        N = kw["n_agents"]
-        env = rware_amd.WarehouseVecEnv(B, library=LIB, **kw)
-        assert env.engines[0].info.envs_per_workgroup == 4
-        orc = OracleVecEnv(B, **kw)
-        assert np.array_equal(env.reset(seed=4)[0], orc.reset(seed=4))
-        rng = np.random.default_rng(0)
-        for rnd in range(2):
-            for t in range(5):
-                a = rng.choice(5, size=(B, N), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-                o, r, d, _, _ = env.step(a)
-                o2, r2, d2 = orc.step_autoreset(a, "next_step")
-                assert np.array_equal(o, o2) and np.array_equal(r, r2) and np.array_equal(d, d2.astype(bool)), (env_id, rnd, t)
-            acts = rng.choice(5, size=(6, B, N), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-            obs, rew, term = env.rollout(acts)        # the 8-env rollout build on the state the 4-env step kernel left, and back
-            for t in range(6):
-                o2, r2, d2 = orc.step_autoreset(acts[t], "next_step")
-                assert np.array_equal(obs[t], o2) and np.array_equal(rew[t], r2) and np.array_equal(term[t], d2.astype(bool)), (env_id, rnd, t)
-        st, so = env.get_state(), orc.get_state()
-        assert all(np.array_equal(st[k], so[k]) for k in so), env_id
-        env.close()
+    # (the 8-env rollout build on the state the 4-env step kernel left, and back)
+    ec.steps_interleaved_with_rollouts((("rware-large-16ag-v1", 32), ("rware-medium-13ag-v1", 128), ("rware-small-10ag-v1", 16), ("rware-small-19ag-v1", 16)),
+                                       max_steps=9, seed=4, rng_seed=0, n_step=5, n_roll=6, rollout_obs=True, library=LIB)
 
 
 @pytest.mark.parametrize("env_id,extra,B,mode", [
@@ -1073,27 +798,13 @@ def test_emulated_pipelined_build_matches_oracle(env_id, extra, B, mode):
     """The chunk-pipelined persistent build of the per-step kernel (rware_kernels.h "PIPE", opt-in: pipe=True): two workgroups walk
     the batch's chunks through two LDS buffers, the next chunk's agent phases beside this chunk's observation stores.  Resets
     (rw_reset, autoreset in both modes) go through the classic kernel on the same state."""
-    kw = rware_amd.env_kwargs(env_id)
-    kw.update(extra)
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
-    env = rware_amd.WarehouseVecEnv(B, autoreset_mode=mode, library=LIB, pipe=True, **kw)
+    kw = oracle_kwargs(env_id, **extra)
+    env, orc = ec.make_pair(B, kw, library=LIB, autoreset_mode=mode, pipe=True)
     info = env.engines[0].info
     assert info.pipe_workgroups in (1, 2) and B % info.pipe_envs_per_workgroup == 0
-    orc = OracleVecEnv(B, **kw)
-    obs, _ = env.reset(seed=7)
-    assert np.array_equal(obs, orc.reset(seed=7))
     rng = np.random.default_rng(3)
-    for t in range(50):
-        a = rng.choice(5, size=(B, kw["n_agents"]), p=[0.1, 0.55, 0.1, 0.1, 0.15]).astype(np.int32)
-        obs, rew, term, trunc, inf = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, mode)
-        assert np.array_equal(obs, o2), t
-        assert np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
-        if mode == "same_step" and d2.any():
-            assert np.array_equal(inf["final_obs"][orc.final_mask], orc.final_obs[orc.final_mask]), t
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
+    lockstep(env, orc, lambda t: rng.choice(5, size=(B, kw["n_agents"]), p=[0.1, 0.55, 0.1, 0.1, 0.15]).astype(np.int32), mode,
+             seed=7, steps=50)
     env.close()
 
 
@@ -1107,8 +818,7 @@ def test_emulated_pipelined_build_is_opt_in():
     env.close()
 
 
-SQUARE5 = dict(shelf_columns=3, column_height=3, shelf_rows=2, n_agents=5, msg_bits=0, sensor_range=2,
-               request_queue_size=3, max_inactivity_steps=None, max_steps=12, reward_type=1)   # a 10 x 10 grid
+SQUARE5 = ec.square(max_steps=12)
 
 
 @pytest.mark.parametrize("kw,extra,B,geom", [
@@ -1122,12 +832,7 @@ SQUARE5 = dict(shelf_columns=3, column_height=3, shelf_rows=2, n_agents=5, msg_b
 def test_emulated_image_terminal_observations_same_step(kw, extra, B, geom):
     """SAME_STEP autoreset with IMAGE / IMAGE_DICT observations: the image (and feature vectors) the terminating step itself produced
     (rware/warehouse.py:527-596, 722-744, 929-946) are kept as info["final_obs"] — round 5 closes the hole FLATTENED / DICT never had."""
-    kw = dict(kw, reward_type=rware_amd.enums.enum_value(kw["reward_type"]))
-    env = rware_amd.WarehouseVecEnv(B, autoreset_mode="same_step", library=LIB, envs_per_workgroup=geom[0], threads_per_workgroup=geom[1], **kw, **extra)
-    orc = OracleVecEnv(B, **kw, **extra)
-    n = gu.check_same_step_image_run(env, orc, B, kw["n_agents"], steps=45, seed=5)
-    assert n > 0
-    env.close()
+    assert ec.image_terminal_observations(oracle_kwargs(**kw, **extra), B, steps=45, seed=5, library=LIB, geom=geom) > 0
 
 
 def test_rw_multi_launcher_threads_overlap_the_enqueues(monkeypatch):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+import lockstep
 from rware_oracle import OracleVecEnv
 
 import rware_amd
@@ -75,27 +76,27 @@ def replay_trace_with_counters(name, lib, steps, tile=1, want_build=None, **geom
 
 
 def check_against_oracle(lib, env_id, extra, B, T, mode, geom=(0, 0), p=(.1, .55, .1, .1, .15), seed=17, jit=None):
-    kw = rware_amd.env_kwargs(env_id)
-    kw.update(extra)
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
+    kw = lockstep.oracle_kwargs(env_id, **extra)
     env = rware_amd.WarehouseVecEnv(B, autoreset_mode=mode, library=lib, stats=True, envs_per_workgroup=geom[0],
                                     threads_per_workgroup=geom[1], jit=jit, **kw)
     assert not jit or env.engines[0].info.jit in (1, 2), env.engines[0].jit_log()
     orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=seed)[0], orc.reset(seed=seed))
     rng = np.random.default_rng(seed)
     M = kw.get("msg_bits", 0)
-    for t in range(T):
+
+    def act(t):
         a = rng.choice(5, size=(B, kw["n_agents"]), p=list(p)).astype(np.int32)
         if M:
             a = np.concatenate([a[..., None], rng.integers(0, 2, size=(B, kw["n_agents"], M), dtype=np.int32)], axis=-1)
-        _, rew, term, _, info = env.step(a)
-        _, r2, d2 = orc.step_autoreset(a, mode)
-        assert np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
+        return a
+
+    def counters(t, obs, rew, term, info):
         assert "deliveries" not in info and "failed_moves" not in info   # the reference's info is {} (:746-747): the counters are a method
         c = env.event_counters()
         assert np.array_equal(c["deliveries"], orc.stat_deliveries), ("deliveries", t)
         assert np.array_equal(c["failed_moves"], orc.stat_failed_moves), ("failed moves", t)
+
+    lockstep.lockstep(env, orc, act, mode, seed=seed, steps=T, on_step=counters)
     totals = int(orc.stat_deliveries.sum()), int(orc.stat_failed_moves.sum())
     env.close()
     return totals
@@ -221,22 +222,19 @@ def test_emulated_pipelined_build_counts_too(monkeypatch):
     """the chunk-pipelined persistent flow (a `make PIPE=1` library; the emulation build carries it) with counters: the service wavefront
     counts per chunk, several chunks per workgroup"""
     monkeypatch.setenv("RWARE_PIPE_GRID", "2")
-    kw = rware_amd.env_kwargs("rware-small-4ag-v1")
-    kw["max_steps"] = 14
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
+    kw = lockstep.oracle_kwargs("rware-small-4ag-v1", max_steps=14)
     B = 96   # 6 chunks of 16 envs on 2 persistent workgroups
     env = rware_amd.WarehouseVecEnv(B, library=_emu(), stats=True, pipe=True, **kw)
     assert env.engines[0].info.pipe_workgroups == 2 and env.engines[0].info.stats == 1
     orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=12)[0], orc.reset(seed=12))
     rng = np.random.default_rng(12)
-    for t in range(35):
-        a = rng.choice(5, size=(B, 4), p=[.05, .7, .1, .1, .05]).astype(np.int32)
-        _, rew, _, _, _ = env.step(a)
-        _, r2, _ = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(rew, r2), t
+
+    def counters(t, obs, rew, term, info):
         c = env.event_counters()
         assert np.array_equal(c["deliveries"], orc.stat_deliveries) and np.array_equal(c["failed_moves"], orc.stat_failed_moves), t
+
+    lockstep.lockstep(env, orc, lambda t: rng.choice(5, size=(B, 4), p=[.05, .7, .1, .1, .05]).astype(np.int32), seed=12, steps=35,
+                      on_step=counters)
     assert orc.stat_failed_moves.sum() > 0
     env.close()
 
@@ -250,12 +248,8 @@ def test_emulated_sharded_env_gathers_its_counters():
     env = rware_amd.WarehouseVecEnv(B, library=_emu(), devices=[0, 0, 0], stats=True, **kw)
     assert len(env.engines) == 3
     orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=3)[0], orc.reset(seed=3))
     rng = np.random.default_rng(9)
-    for t in range(30):
-        a = rng.choice(5, size=(B, 2), p=[.05, .7, .1, .1, .05]).astype(np.int32)
-        env.step(a)
-        orc.step_autoreset(a, "next_step")
+    lockstep.lockstep(env, orc, lambda t: rng.choice(5, size=(B, 2), p=[.05, .7, .1, .1, .05]).astype(np.int32), seed=3, steps=30)
     c = env.event_counters()
     assert c["deliveries"].shape == (B,) and np.array_equal(c["deliveries"], orc.stat_deliveries)
     assert np.array_equal(c["failed_moves"], orc.stat_failed_moves) and orc.stat_failed_moves.sum() > 0

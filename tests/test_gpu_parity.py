@@ -5,14 +5,14 @@
 bit-exact on every field (grid, agent SoA, queue, counters, PCG64 state, obs, rewards, done)."""
 import os
 import re
-from collections import Counter
 
 import numpy as np
 import pytest
 
-import collision_scenarios as cs
+import engine_checks as ec
 import golden_util as gu
 from engine_backend import EngineBackend
+from lockstep import check_rollout, lockstep, oracle_kwargs, same_obs
 from rware_oracle import OracleVecEnv
 
 import rware_amd
@@ -85,34 +85,17 @@ CASES = [
 @pytest.mark.parametrize("env_id,extra,B,T,geom", CASES)
 @pytest.mark.parametrize("mode", ["next_step", "same_step"])
 def test_engine_matches_oracle_large_batch(env_id, extra, B, T, geom, mode):
-    kw = rware_amd.env_kwargs(env_id)
-    kw.update(extra)
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
-    env = rware_amd.WarehouseVecEnv(B, autoreset_mode=mode, envs_per_workgroup=geom[0],
-                                    threads_per_workgroup=geom[1], **kw)
-    orc = OracleVecEnv(B, **kw)
-    seed = 31337
-    obs, _ = env.reset(seed=seed)
-    assert np.array_equal(obs, orc.reset(seed=seed))
+    kw = oracle_kwargs(env_id, **extra)
+    env, orc = ec.make_pair(B, kw, geom=geom, autoreset_mode=mode)
     rng = np.random.default_rng(5)
     N = kw["n_agents"]
-    for t in range(T):
+
+    def act(t):
         p = [0.2] * 5 if (t // 50) % 2 == 0 else [0.1, 0.6, 0.1, 0.1, 0.1]
-        a = rng.choice(5, size=(B, N), p=p).astype(np.int32)
-        obs, rew, term, trunc, info = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, mode)
-        assert np.array_equal(rew, r2), f"rewards t={t}"
-        assert np.array_equal(term, d2.astype(bool)), f"done t={t}"
-        assert np.array_equal(obs, o2), f"obs t={t}"
-        if mode == "same_step":   # the pre-reset observation of the terminating step (rware/warehouse.py:929-946): info["final_obs"]
-            assert ("final_obs" in info) == bool(d2.any()), t
-            if d2.any():
-                assert np.array_equal(info["_final_obs"], orc.final_mask)
-                assert np.array_equal(info["final_obs"][orc.final_mask], orc.final_obs[orc.final_mask]), f"final_obs t={t}"
-        if t % 25 == 0 or t == T - 1:
-            st, so = env.get_state(), orc.get_state()
-            for k in so:
-                assert np.array_equal(st[k], so[k]), f"{k} t={t}"
+        return rng.choice(5, size=(B, N), p=p).astype(np.int32)
+
+    # (same_step: the pre-reset observation of the terminating step (rware/warehouse.py:929-946), info["final_obs"])
+    lockstep(env, orc, act, mode, seed=31337, steps=T, state_every=25)
     env.close()
 
 
@@ -275,22 +258,12 @@ def test_full_size_headline_batch_properties():
 ])
 def test_fused_rollout_matches_oracle(env_id, extra, B, mode):
     """rw_step_many_device: T steps in one launch with the env chunk resident in LDS == T oracle steps."""
-    kw = rware_amd.env_kwargs(env_id)
-    kw.update(extra)
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
-    env = rware_amd.WarehouseVecEnv(B, autoreset_mode=mode, **kw)
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=77)[0], orc.reset(seed=77))
+    kw = oracle_kwargs(env_id, **extra)
+    env, orc = ec.make_pair(B, kw, autoreset_mode=mode)
+    same_obs(env.reset(seed=77)[0], orc.reset(seed=77), "reset obs", "reset")
     T = 530 if not extra.get("max_steps") else 160
     acts = np.random.default_rng(9).choice(5, size=(T, B, kw["n_agents"]), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-    obs, rew, term = env.rollout(acts)
-    for t in range(T):
-        o2, r2, d2 = orc.step_autoreset(acts[t], mode)
-        assert np.array_equal(rew[t], r2) and np.array_equal(term[t], d2.astype(bool)), t
-        assert np.array_equal(obs[t], o2), t
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
+    check_rollout(env, orc, acts, mode)
     env.close()
 
 
@@ -319,29 +292,8 @@ def test_snapshot_restore_on_device():
     ("rware-medium-6ag-hard-v1", 3, False, 2, 1024),
 ])
 def test_image_observations_match_oracle(env_id, obs_type, directional, sr, B):
-    kw = rware_amd.env_kwargs(env_id)
-    kw.update(sensor_range=sr, max_steps=60)
-    kw["reward_type"] = kw["reward_type"].value
-    extra = dict(observation_type=obs_type, image_observation_directional=directional)
-    env = rware_amd.WarehouseVecEnv(B, **kw, **extra)
-    orc = OracleVecEnv(B, **kw, **extra)
-
-    def same(a, b):
-        if isinstance(a, dict):
-            return np.array_equal(a["image"], b[0]) and np.array_equal(a["features"], b[1])
-        return np.array_equal(a, b)
-
-    assert same(env.reset(seed=4)[0], orc.reset(seed=4))
-    acts = np.random.default_rng(7).choice(5, size=(130, B, kw["n_agents"]), p=[.1, .5, .15, .15, .1])
-    for t in range(130):
-        o, r, d, _, _ = env.step(acts[t])
-        o2, r2, d2 = orc.step_autoreset(acts[t], "next_step")
-        assert same(o, o2) and np.array_equal(r, r2) and np.array_equal(d, d2.astype(bool)), t
-    env.close()
-
-
-SQUARE = dict(shelf_columns=3, column_height=3, shelf_rows=2, n_agents=5, msg_bits=0, sensor_range=2,
-              request_queue_size=3, max_inactivity_steps=None, max_steps=60, reward_type=1)   # a 10 x 10 grid
+    kw = oracle_kwargs(env_id, sensor_range=sr, max_steps=60, observation_type=obs_type, image_observation_directional=directional)
+    ec.image_observations(kw, B, tape_steps=130, n_step=130)
 
 
 @pytest.mark.parametrize("obs_type,directional,layers,B", [
@@ -352,57 +304,14 @@ def test_transposed_image_layers_match_oracle(obs_type, directional, layers, B):
     """AGENT_DIRECTION / AGENT_LOAD exactly as the reference writes them (layer[ag.x, ag.y], :552/:558), on a
     square grid where that index is always in bounds; per-step and fused rollout."""
     extra = dict(observation_type=obs_type, image_observation_directional=directional, image_observation_layers=layers)
-    env = rware_amd.WarehouseVecEnv(B, **SQUARE, **extra)
-    orc = OracleVecEnv(B, **SQUARE, **extra)
-
-    def same(a, b):
-        if isinstance(a, dict):
-            return np.array_equal(a["image"], b[0]) and np.array_equal(a["features"], b[1])
-        return np.array_equal(a, b)
-
-    assert same(env.reset(seed=4)[0], orc.reset(seed=4))
-    acts = np.random.default_rng(7).choice(5, size=(150, B, 5), p=[.1, .45, .15, .15, .15])
-    for t in range(110):
-        o, r, d, _, _ = env.step(acts[t])
-        o2, r2, d2 = orc.step_autoreset(acts[t], "next_step")
-        assert same(o, o2) and np.array_equal(r, r2) and np.array_equal(d, d2.astype(bool)), t
-    img, rew, term = env.rollout(acts[110:])
-    for t in range(110, 150):
-        o2, r2, d2 = orc.step_autoreset(acts[t], "next_step")
-        assert np.array_equal(img[t - 110], o2[0] if isinstance(o2, tuple) else o2) and np.array_equal(rew[t - 110], r2), t
-    env.close()
+    ec.transposed_image_layers(extra, layers, B, max_steps=60, seed=4, rng_seed=7, tape_steps=150, n_step=110)
 
 
 @pytest.mark.parametrize("layer", [3, 4])
 def test_transposed_image_layers_raise_indexerror_like_the_reference(layer):
     """Registered layouts have H > W: the reference's transposed write raises IndexError once an agent (a loaded
     one for AGENT_LOAD) stands at y >= W; the engine reports it for the same reset()/step() call."""
-    kw = rware_amd.env_kwargs("rware-small-4ag-v1")
-    kw["reward_type"] = kw["reward_type"].value
-    extra = dict(observation_type=2, image_observation_layers=[2, layer])
-    B = 64 if layer == 3 else 8
-    env = rware_amd.WarehouseVecEnv(B, **kw, **extra)
-    orc = OracleVecEnv(B, **kw, **extra)
-    rng = np.random.default_rng(1)
-
-    def attempt(f):
-        try:
-            return f(), False
-        except IndexError:
-            return None, True
-
-    (o, e1), (o2, e2) = attempt(lambda: env.reset(seed=2)[0]), attempt(lambda: orc.reset(seed=2))
-    assert e1 == e2
-    t = 0
-    while not e1 and t < 600:
-        a = rng.choice(5, size=(B, 4), p=[.05, .5, .15, .15, .15])
-        (res, e1), (res2, e2) = attempt(lambda: env.step(a)), attempt(lambda: orc.step_autoreset(a, "next_step"))
-        assert e1 == e2, t
-        if not e1:
-            assert np.array_equal(res[0], res2[0]), t
-        t += 1
-    assert e1, "no agent ever reached y >= W"
-    env.close()
+    ec.transposed_layers_raise_indexerror("rware-small-4ag-v1", layer, 64 if layer == 3 else 8, limit=600)
 
 
 def test_dict_observations_are_the_unflattened_oracle_vector():
@@ -833,32 +742,18 @@ PAPER_GRID = [f"rware-{size}-{n}ag{diff}-v1" for size in ("tiny", "small", "medi
 def test_paper_task_grid_exact_shape_builds_match_oracle(env_id):
     """Every task of the RWARE papers' grid (tiny / small / medium x 2, 4, 6, 8 agents x easy / normal / hard) runs an exact-shape
     kernel build; each against the oracle on every env, per-step launches and a fused rollout, across autoresets."""
-    kw = rware_amd.env_kwargs(env_id)
-    kw["max_steps"] = 50
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
+    kw = oracle_kwargs(env_id, max_steps=50)
     B, N = 512, kw["n_agents"]
     # 6 and 8 agents have two builds (8 envs per workgroup up to 16384 envs, 16 beyond): alternate which one is pinned
     # (2 agents: 16 envs per workgroup below 16384 envs, 32 from there on — every 2-agent id is pinned to the 32-env build here)
     geom = (16, 256) if N >= 6 and len(env_id) % 2 else (32, 256) if N == 2 else (0, 0)
-    env = rware_amd.WarehouseVecEnv(B, envs_per_workgroup=geom[0], threads_per_workgroup=geom[1], **kw)
+    env, orc = ec.make_pair(B, kw, geom=geom)
     assert env.engines[0].info.specialised == 1
     assert env.engines[0].info.envs_per_workgroup == (geom[0] if geom[0] else 16 if N < 6 else 8)
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=31)[0], orc.reset(seed=31))
     rng = np.random.default_rng(8)
-    for t in range(70):
-        a = rng.choice(5, size=(B, N), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
+    lockstep(env, orc, lambda t: rng.choice(5, size=(B, N), p=[.1, .55, .1, .1, .15]).astype(np.int32), seed=31, steps=70)
     acts = rng.choice(5, size=(40, B, N), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-    obs, rew, term = env.rollout(acts)
-    for k in range(40):
-        o2, r2, d2 = orc.step_autoreset(acts[k], "next_step")
-        assert np.array_equal(obs[k], o2) and np.array_equal(rew[k], r2) and np.array_equal(term[k], d2.astype(bool)), k
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
+    check_rollout(env, orc, acts, t0=70)
     env.close()
 
 
@@ -875,28 +770,14 @@ def test_agent_count_static_builds_match_oracle(env_id):
     """Registered ids without an exact (N, Q) entry — odd agent counts, the large warehouse — run the agent-count-static
     build of their size and agent count (request-queue length read at run time): against the oracle on every env, per-step
     launches and a fused rollout, across autoresets."""
-    kw = rware_amd.env_kwargs(env_id)
-    kw["max_steps"] = 45
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
+    kw = oracle_kwargs(env_id, max_steps=45)
     B, N = 512, kw["n_agents"]
-    env = rware_amd.WarehouseVecEnv(B, **kw)
+    env, orc = ec.make_pair(B, kw)
     assert env.engines[0].info.build_kind == 2
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=41)[0], orc.reset(seed=41))
     rng = np.random.default_rng(9)
-    for t in range(60):
-        a = rng.choice(5, size=(B, N), p=[.1, .5, .1, .1, .2]).astype(np.int32)
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
+    lockstep(env, orc, lambda t: rng.choice(5, size=(B, N), p=[.1, .5, .1, .1, .2]).astype(np.int32), seed=41, steps=60)
     acts = rng.choice(5, size=(40, B, N), p=[.1, .5, .1, .1, .2]).astype(np.int32)
-    obs, rew, term = env.rollout(acts)
-    for k in range(40):
-        o2, r2, d2 = orc.step_autoreset(acts[k], "next_step")
-        assert np.array_equal(obs[k], o2) and np.array_equal(rew[k], r2) and np.array_equal(term[k], d2.astype(bool)), k
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
+    check_rollout(env, orc, acts, t0=60)
     env.close()
 
 
@@ -916,36 +797,8 @@ def test_crowded_warehouses_resolve_long_chains(env_id, p_forward, geom):
     tiny-12ag-easy 2 / 4 / 45 / 348 / 2270, tiny-13ag 1 / 4 / 57 / 391 / 2852, tiny-16ag 3 / 5 / 98 / 518 / 3798,
     tiny-17ag-hard 5 / 4 / 121 / 632 / 3417, tiny-19ag 7 / 5 / 150 / 591 / 6041, small-16ag 0 / 3 / 51 / 432 / 3555,
     small-19ag 4 / 4 / 87 / 548 / 4788.  The rare structures are pinned by construction in test_collision_structures.py."""
-    kw = rware_amd.env_kwargs(env_id)
-    kw["max_steps"] = 60
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
-    B, N = 256, kw["n_agents"]
-    env = rware_amd.WarehouseVecEnv(B, envs_per_workgroup=geom[0], threads_per_workgroup=geom[1], **kw)
-    assert env.engines[0].info.build_kind == 2 and env.engines[0].info.envs_per_workgroup == (geom[0] or 8)
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=31)[0], orc.reset(seed=31))
-    rng = np.random.default_rng(33)
-    rest = (1.0 - p_forward) / 4
-    seen = Counter()
-    for t in range(150):
-        a = rng.choice(5, size=(B, N), p=[rest, p_forward, rest, rest, rest]).astype(np.int32)
-        so = orc.get_state()
-        for e in range(64):                                     # what this step is made of: the oracle's pre-step state, a quarter of the envs
-            seen.update(cs.analyse(so["agent_x"][e], so["agent_y"][e], so["agent_dir"][e], so["agent_carry"][e], a[e], orc.H, orc.W, so["grid"][e, 1])[0])
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
-    print(f"census {env_id} (64 envs x 150 steps): {dict(sorted(seen.items()))}")
-    assert seen
-    acts = rng.choice(5, size=(25, B, N), p=[rest, p_forward, rest, rest, rest]).astype(np.int32)
-    obs, rew, term = env.rollout(acts)                      # the fused rollout keeps the all-gather (register) agent phases
-    for k in range(25):
-        o2, r2, d2 = orc.step_autoreset(acts[k], "next_step")
-        assert np.array_equal(obs[k], o2) and np.array_equal(rew[k], r2) and np.array_equal(term[k], d2.astype(bool)), k
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
-    env.close()
+    # (the census: the oracle's pre-step state of a quarter of the envs)
+    ec.crowded_warehouse(env_id, p_forward, 256, max_steps=60, n_step=150, envs_per_workgroup=geom[0] or 8, census=64, geom=geom)
 
 
 def test_dpp_subrev_probe_on_this_gpu(tmp_path):
@@ -1014,24 +867,7 @@ def test_generic_kernel_matches_oracle_on_random_shapes(case):
     B = int(g.integers(40, 400))
     mode = ["next_step", "same_step"][case % 2]
     E, T = int(g.choice([4, 8, 12])), int(g.choice([64, 128, 256]))
-    env = rware_amd.WarehouseVecEnv(B, envs_per_workgroup=E, threads_per_workgroup=T, autoreset_mode=mode, **kw)
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=90 + case)[0], orc.reset(seed=90 + case))
-    rng = np.random.default_rng(case)
-    for t in range(90):
-        a = rng.choice(5, size=(B, n_agents), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, mode)
-        assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), (t, kw, B, E, T)
-    acts = rng.choice(5, size=(30, B, n_agents), p=[.1, .55, .1, .1, .15]).astype(np.int32)
-    obs, rew, term = env.rollout(acts)
-    for k in range(30):
-        o2, r2, d2 = orc.step_autoreset(acts[k], mode)
-        assert np.array_equal(obs[k], o2) and np.array_equal(rew[k], r2) and np.array_equal(term[k], d2.astype(bool)), (k, kw)
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), (k, kw)
-    env.close()
+    ec.random_shape(kw, B, mode, (E, T), case=case, seed=90 + case, n_step=90, n_roll=30)
 
 
 def test_capture_loop_replays_policy_and_step_from_one_graph():
@@ -1124,7 +960,7 @@ def test_corrupt_cached_code_object_is_dropped_and_recompiled(tmp_path, monkeypa
     a good cache again.  (rware_jit.cpp's own handling of malformed cache files runs under ASAN in oracle/sanitize.sh.)"""
     monkeypatch.setenv("RWARE_JIT_CACHE", str(tmp_path))
     kw = dict(rware_amd.env_kwargs("rware-tiny-2ag-v1"), n_agents=3, request_queue_size=3, column_height=5, max_steps=30)
-    okw = dict(kw, reward_type=rware_amd.enums.enum_value(kw["reward_type"]))
+    okw = oracle_kwargs(**kw)
     B = 512
     env = rware_amd.WarehouseVecEnv(B, jit="force", **kw)
     assert env.engines[0].info.jit == 1, env.engines[0].jit_log()
@@ -1143,13 +979,8 @@ def test_corrupt_cached_code_object_is_dropped_and_recompiled(tmp_path, monkeypa
     assert eng.info.jit == 1 and eng.info.build_kind == 1, log                      # compiled afresh, not the generic kernel
     assert "loading the code object failed" in log and "dropped the cached file" in log and "retry" in log, log
     orc = OracleVecEnv(B, **okw)
-    assert np.array_equal(env.reset(seed=5)[0], orc.reset(seed=5))
     rng = np.random.default_rng(6)
-    for t in range(40):
-        a = rng.integers(0, 5, size=(B, 3)).astype(np.int32)
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
+    lockstep(env, orc, lambda t: rng.integers(0, 5, size=(B, 3)).astype(np.int32), seed=5, steps=40)
     env.close()
     env = rware_amd.WarehouseVecEnv(B, jit="force", **kw)
     assert env.engines[0].info.jit == 2, env.engines[0].jit_log()                    # the cache is good again
@@ -1188,13 +1019,7 @@ def test_runtime_specialisation_policy(tmp_path, monkeypatch):
         assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
         assert np.array_equal(ob2, o2) and np.array_equal(rw2, r2), t
     acts = rng.choice(5, size=(20, B, N), p=[.1, .5, .1, .1, .2]).astype(np.int32)
-    obs, rew, term = env.rollout(acts)                       # the specialised fused-rollout kernel
-    for k in range(20):
-        o2, r2, d2 = orc.step_autoreset(acts[k], "next_step")
-        assert np.array_equal(obs[k], o2) and np.array_equal(rew[k], r2) and np.array_equal(term[k], d2.astype(bool)), k
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
+    check_rollout(env, orc, acts, t0=90)                     # the specialised fused-rollout kernel
     env.close(); off.close()
     # the run-time compiled build of a REGISTERED shape at 16 workgroups per CU: the same kernel source as the ahead-of-time
     # build next to it, every observation of every env
@@ -1304,21 +1129,11 @@ def test_start_stagger_rule_for_13_to_16_agents_matches_oracle():
         assert env.engines[0].info.stagger_ticks == want, (env_id, extra, B)
         env.close()
     for env_id, B in (("rware-medium-13ag-v1", 16384), ("rware-large-16ag-v1", 16384)):
-        kw = rware_amd.env_kwargs(env_id)
-        kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
-        kw["max_steps"] = 20
-        env = rware_amd.WarehouseVecEnv(B, **kw)
+        kw = oracle_kwargs(env_id, max_steps=20)
+        env, orc = ec.make_pair(B, kw)
         assert env.engines[0].info.stagger_ticks == 55
-        orc = OracleVecEnv(B, **kw)
-        assert np.array_equal(env.reset(seed=9)[0], orc.reset(seed=9))
         rng = np.random.default_rng(2)
-        for t in range(45):
-            a = rng.choice(5, size=(B, kw["n_agents"]), p=[0.1, 0.55, 0.1, 0.1, 0.15]).astype(np.int32)
-            obs, rew, term, _, _ = env.step(a)
-            o2, r2, d2 = orc.step_autoreset(a, "next_step")
-            assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), (env_id, t)
-        st, so = env.get_state(), orc.get_state()
-        assert all(np.array_equal(st[k], so[k]) for k in so)
+        lockstep(env, orc, lambda t: rng.choice(5, size=(B, kw["n_agents"]), p=[0.1, 0.55, 0.1, 0.1, 0.15]).astype(np.int32), seed=9, steps=45)
         env.close()
 
 
@@ -1397,31 +1212,9 @@ def test_13_to_16_agents_step_on_4_env_workgroups_and_roll_out_on_8(monkeypatch)
     env.close()
     monkeypatch.delenv("RWARE_WIDE_E4")
     # (9 .. 12 agents: the fused rollout follows onto the 4-env build; 13 .. 19: it stays on the 8-env one)
-    for env_id, B in (("rware-large-16ag-v1", 4096), ("rware-medium-13ag-v1", 32768), ("rware-small-15ag-v1", 8192), ("rware-small-10ag-v1", 4096),
-                      ("rware-small-19ag-v1", 6144)):
-        kw = rware_amd.env_kwargs(env_id)
-        kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
-        kw["max_steps"] = 17
-        N = kw["n_agents"]
-        env = rware_amd.WarehouseVecEnv(B, **kw)
-        assert env.engines[0].info.envs_per_workgroup == 4
-        orc = OracleVecEnv(B, **kw)
-        assert np.array_equal(env.reset(seed=9)[0], orc.reset(seed=9))
-        rng = np.random.default_rng(2)
-        for rnd in range(2):
-            for t in range(12):
-                a = rng.choice(5, size=(B, N), p=[0.1, 0.55, 0.1, 0.1, 0.15]).astype(np.int32)
-                obs, rew, term, _, _ = env.step(a)
-                o2, r2, d2 = orc.step_autoreset(a, "next_step")
-                assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), (env_id, rnd, t)
-            tape = rng.choice(5, size=(8, B, N), p=[0.1, 0.55, 0.1, 0.1, 0.15]).astype(np.int32)
-            _, rew, term = env.rollout(tape, want_obs=False)
-            for t in range(8):
-                _, r2, d2 = orc.step_autoreset(tape[t], "next_step")
-                assert np.array_equal(rew[t], r2) and np.array_equal(term[t], d2.astype(bool)), (env_id, rnd, t)
-        st, so = env.get_state(), orc.get_state()
-        assert all(np.array_equal(st[k], so[k]) for k in so), env_id
-        env.close()
+    ec.steps_interleaved_with_rollouts((("rware-large-16ag-v1", 4096), ("rware-medium-13ag-v1", 32768), ("rware-small-15ag-v1", 8192),
+                                        ("rware-small-10ag-v1", 4096), ("rware-small-19ag-v1", 6144)),
+                                       max_steps=17, seed=9, rng_seed=2, n_step=12, n_roll=8, rollout_obs=False)
 
 
 def test_two_pipelines_on_one_device_match_the_single_engine():
@@ -1557,21 +1350,14 @@ def test_pipe_request_on_the_default_library_runs_the_classic_kernel_and_says_so
     shows it and `rw_jit_log()` says why — nothing fails, nothing is silently different."""
     if _library_has_pipelined_builds():
         pytest.skip("this library was built with PIPE=1")
-    kw = rware_amd.env_kwargs("rware-small-4ag-v1")
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
+    kw = oracle_kwargs("rware-small-4ag-v1")
     B = 256
-    env = rware_amd.WarehouseVecEnv(B, pipe=True, **kw)
+    env, orc = ec.make_pair(B, kw, pipe=True)
     eng = env.engines[0]
     assert eng.info.pipe_workgroups == 0 and eng.info.specialised == 1
     assert "make PIPE=1" in eng.jit_log()
-    orc = OracleVecEnv(B, **kw)
-    assert np.array_equal(env.reset(seed=3)[0], orc.reset(seed=3))
     rng = np.random.default_rng(3)
-    for t in range(30):
-        a = rng.integers(0, 5, size=(B, 4)).astype(np.int32)
-        obs, rew, term, _, _ = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, "next_step")
-        assert np.array_equal(obs, o2) and np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
+    lockstep(env, orc, lambda t: rng.integers(0, 5, size=(B, 4)).astype(np.int32), seed=3, steps=30)
     env.close()
 
 
@@ -1600,28 +1386,14 @@ def test_pipelined_builds_replay_reference_golden(name, tile, grid, monkeypatch)
     ("rware-large-16ag-v1", {"max_steps": 30}, 16384, 70, "next_step"),
 ])
 def test_pipelined_builds_match_oracle_full_batch(env_id, extra, B, T, mode):
-    kw = rware_amd.env_kwargs(env_id)
-    kw.update(extra)
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
+    kw = oracle_kwargs(env_id, **extra)
     if not _library_has_pipelined_builds():
         pytest.skip("librware_hip.so was built without the pipelined kernels (make PIPE=1): quarantined, measured slower everywhere")
-    env = rware_amd.WarehouseVecEnv(B, autoreset_mode=mode, pipe=True, **kw)
+    env, orc = ec.make_pair(B, kw, autoreset_mode=mode, pipe=True)
     assert env.engines[0].info.pipe_workgroups > 0
-    orc = OracleVecEnv(B, **kw)
-    obs, _ = env.reset(seed=11)
-    assert np.array_equal(obs, orc.reset(seed=11))
     rng = np.random.default_rng(5)
-    for t in range(T):
-        a = rng.choice(5, size=(B, kw["n_agents"]), p=[0.1, 0.55, 0.1, 0.1, 0.15]).astype(np.int32)
-        obs, rew, term, trunc, info = env.step(a)
-        o2, r2, d2 = orc.step_autoreset(a, mode)
-        assert np.array_equal(rew, r2) and np.array_equal(term, d2.astype(bool)), t
-        assert np.array_equal(obs, o2), t
-        if mode == "same_step" and d2.any():
-            assert np.array_equal(info["final_obs"][orc.final_mask], orc.final_obs[orc.final_mask]), t
-    st, so = env.get_state(), orc.get_state()
-    for k in so:
-        assert np.array_equal(st[k], so[k]), k
+    lockstep(env, orc, lambda t: rng.choice(5, size=(B, kw["n_agents"]), p=[0.1, 0.55, 0.1, 0.1, 0.15]).astype(np.int32), mode,
+             seed=11, steps=T)
     env.close()
 
 
@@ -1648,22 +1420,12 @@ def test_library_selftest_guards_run_on_this_gpu(monkeypatch):
 def test_image_terminal_observations_same_step(env_id, extra, B):
     """SAME_STEP autoreset keeps the terminating step's own IMAGE / IMAGE_DICT observation (rware/warehouse.py:
     527-596, 929-946) as info["final_obs"]; compared with the oracle's pre-reset image on every env that ended an episode."""
-    kw = rware_amd.env_kwargs(env_id)
-    kw.update(extra)
-    kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
-    env = rware_amd.WarehouseVecEnv(B, autoreset_mode="same_step", **kw)
-    orc = OracleVecEnv(B, **kw)
-    assert gu.check_same_step_image_run(env, orc, B, kw["n_agents"], steps=100, seed=4) >= 2 * B
-    env.close()
+    assert ec.image_terminal_observations(oracle_kwargs(env_id, **extra), B, steps=100, seed=4) >= 2 * B
 
 
 def test_image_terminal_observations_same_step_transposed_layers():
-    kw = dict(shelf_columns=3, column_height=3, shelf_rows=2, n_agents=5, msg_bits=0, sensor_range=2, request_queue_size=3,
-              max_inactivity_steps=None, max_steps=25, reward_type=1, observation_type=2, image_observation_layers=[3, 4, 0, 1, 2, 5, 6])
-    env = rware_amd.WarehouseVecEnv(2048, autoreset_mode="same_step", **kw)
-    orc = OracleVecEnv(2048, **kw)
-    assert gu.check_same_step_image_run(env, orc, 2048, 5, steps=60, seed=9) >= 2 * 2048
-    env.close()
+    kw = dict(ec.square(max_steps=25), observation_type=2, image_observation_layers=[3, 4, 0, 1, 2, 5, 6])
+    assert ec.image_terminal_observations(kw, 2048, steps=60, seed=9) >= 2 * 2048
 
 
 @pytest.mark.parametrize("env_id,extra,B,T,shards", [
