@@ -134,6 +134,9 @@ class OracleVecEnv:
         self.B, self.N, self.Q, self.R = int(num_envs), int(n_agents), int(request_queue_size), int(sensor_range)
         self.H, self.W = self.hw.shape
         self.S = int((self.hw == 0).sum())
+        if self.Q > 0 and self.Q >= self.S:
+            # the reference raises at the first delivery: np_random.choice([]) (rware/warehouse.py:915-916)
+            raise ValueError(f"request_queue_size {self.Q} >= {self.S} shelves: no shelf is left to request after a delivery")
         self.L = 8 + (7 + self.M) * (2 * self.R + 1) ** 2
         self.cfg = _Cfg(self.H, self.W, self.N, self.Q, self.R, len(self.goals),
                         int(max_inactivity_steps or 0), int(max_steps or 0), reward_type,

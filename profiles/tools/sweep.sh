@@ -11,6 +11,9 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/sweep_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
+# every profiled run under a time limit of its own; a run that fails, faults or runs into its limit ends the sweep
+LIMIT="timeout -k 10 ${SWEEP_STEP_TIMEOUT:-300}"
+stop() { echo "sweep: $1 ended with exit status $2: stopping" >&2; exit "$2"; }
 COMMON="--no-cpu-baseline --no-hbm-regime --no-api-loop --no-fused-extra --no-submit-modes --no-sustained --no-soak"
 # name | tape steps | trace steps | bench.py arguments
 # (small kernels get long trace runs: rocprofv3 slows the host's first few thousand launches down to ~10 us each, which
@@ -38,7 +41,7 @@ cd /tmp
 if [ -z "$ONLY" ] || [[ "calib" == *"$ONLY"* ]]; then
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -o /tmp/copy_calib "$ROOT/profiles/tools/copy_calib.hip" 2> "$OUT/calib_build.log"
   for c in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --pmc $c -d "$OUT/calib/pmc_$c" -o calib -- /tmp/copy_calib > "$OUT/calib_$c.log" 2>&1
+    $LIMIT rocprofv3 --pmc $c -d "$OUT/calib/pmc_$c" -o calib -- /tmp/copy_calib > "$OUT/calib_$c.log" 2>&1 || stop "calibration $c" $?
   done
 fi
 for entry in "${CONFIGS[@]}"; do
@@ -51,9 +54,9 @@ for entry in "${CONFIGS[@]}"; do
   # dispatches then start late, on an idle chip) — replay the same per-step launches from a HIP graph for the trace pass
   SUBMIT=""
   if [ "$steps" -ge 1000 ] && [[ "$args" != *"--many"* ]] && [ "${SWEEP_TRACE_SUBMIT:-graph}" = "graph" ]; then SUBMIT="--submit graph"; fi
-  rocprofv3 --kernel-trace --stats -d "$D/trace" -o bench -- python "$ROOT/bench.py" $COMMON $args $SUBMIT --steps $steps --warmup 50 > "$D/trace.out" 2> "$D/trace.err"
+  $LIMIT rocprofv3 --kernel-trace --stats -d "$D/trace" -o bench -- python "$ROOT/bench.py" $COMMON $args $SUBMIT --steps $steps --warmup 50 > "$D/trace.out" 2> "$D/trace.err" || stop "$name trace" $?
   for c in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --pmc $c -d "$D/pmc_$c" -o bench -- python "$ROOT/bench.py" $COMMON $args --steps 30 --warmup 10 > "$D/pmc_$c.out" 2> "$D/pmc_$c.err"
+    $LIMIT rocprofv3 --pmc $c -d "$D/pmc_$c" -o bench -- python "$ROOT/bench.py" $COMMON $args --steps 30 --warmup 10 > "$D/pmc_$c.out" 2> "$D/pmc_$c.err" || stop "$name $c" $?
   done
 done
 cd "$ROOT"

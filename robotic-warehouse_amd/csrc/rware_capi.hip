@@ -410,7 +410,9 @@ int check_config(const rw_config *cfg, Shape *out) {
     if (N > HW) return fail(nullptr, RW_ERR_INVALID_ARG, "more agents than cells");
     int S = 0;
     for (int i = 0; i < HW; ++i) S += cfg->highways[i] ? 0 : 1;
-    if (Q > S) return fail(nullptr, RW_ERR_INVALID_ARG, "request_queue_size %d > shelves %d", Q, S);
+    if (Q > 0 && Q >= S)  // (Q == S: the reference builds the env and raises ValueError at its first delivery, choice([]))
+        return fail(nullptr, RW_ERR_INVALID_ARG, "request_queue_size %d >= shelves %d: no shelf is left to request after a delivery "
+                    "(the reference raises ValueError at its first delivery, rware/warehouse.py:915-916)", Q, S);
     if (cfg->n_goals > rw::MAX_GOALS) return fail(nullptr, RW_ERR_UNSUPPORTED, "more than %d goal cells", (int)rw::MAX_GOALS);
     for (int g = 0; g < cfg->n_goals; ++g) {
         const int x = cfg->goals_xy[2 * g], y = cfg->goals_xy[2 * g + 1];

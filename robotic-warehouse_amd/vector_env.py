@@ -179,6 +179,10 @@ class WarehouseVecEnv(_VectorEnvBase):
         if output not in ("numpy", "torch"):
             raise ValueError("output must be 'numpy' or 'torch'")
         self.layout: Layout = layout_from_str(layout) if layout else layout_from_params(shelf_columns, shelf_rows, column_height)
+        n_shelves = self.layout.n_shelves
+        if int(request_queue_size) > 0 and int(request_queue_size) >= n_shelves:
+            # the reference constructs such an env and raises at its first delivery: np_random.choice([]) (rware/warehouse.py:915-916)
+            raise ValueError(f"request_queue_size {int(request_queue_size)} >= {n_shelves} shelves: no shelf is left to request after a delivery")
         self.num_envs = int(num_envs)
         self.n_agents = int(n_agents)
         self.sensor_range = int(sensor_range)

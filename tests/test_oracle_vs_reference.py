@@ -280,14 +280,17 @@ def test_oracle_matches_the_live_reference_on_random_shapes(case):
     env = rr.make_reference_env(None, **dict(kw, reward_type=wh.RewardType(kw["reward_type"])))   # (the reference compares enum members)
     if env.n_agents > (env.grid_size[0] * env.grid_size[1]) // 2:
         pytest.skip("more agents than this tiny grid can hold comfortably")
-    orc = OracleVecEnv(1, **kw)
     seed = 900 + case
     try:
         obs, _ = env.reset(seed=seed)
     except ValueError:
         pytest.skip("a layout without shelves (one column: it is the goal column): the reference's own reset() raises")
     if kw["request_queue_size"] >= len(env.shelfs):
+        if kw["request_queue_size"]:        # (the oracle refuses at construction what the reference refuses at its first delivery)
+            with pytest.raises(ValueError):
+                OracleVecEnv(1, **kw)
         pytest.skip("as many requests as shelves: the reference's own replacement draw has no candidates (ValueError)")
+    orc = OracleVecEnv(1, **kw)
     assert np.array_equal(rr.obs_array(obs), orc.reset(seed=seed)[0])
     pol = np.random.default_rng(seed)
     done_prev = False
