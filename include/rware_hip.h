@@ -30,7 +30,10 @@ extern "C" {
 #endif
 
 /* 4 (since 3): RW_OBS_PACKED in rw_stream_flags, RW_BUF_OBS_PACKED (RW_BUF_KIND_COUNT 22 -> 23), rw_info.obs_packed appended (the struct
- * grows by 8 bytes), rw_unpack_obs, a 16th element (`packed`) in rw_jit_probe's shape.  Everything else is unchanged. */
+ * grows by 8 bytes), rw_unpack_obs, a 16th element (`packed`) in rw_jit_probe's shape.  Everything else is unchanged.
+ * Still 4, a compatible addition: RW_EPISODES_ON in rw_stream_flags, RW_BUF_EP_RETURN .. RW_BUF_EP_COUNT appended (RW_BUF_KIND_COUNT 23 -> 28;
+ * all five empty without the flag), and rw_info.stats read as a bit set — bit 0 RW_STATS_ON, bit 1 RW_EPISODES_ON — so an engine with only
+ * the old flag still reports 1; rw_info keeps its size. */
 #define RW_ABI_VERSION 4
 
 typedef struct rw_engine rw_engine;
@@ -145,7 +148,22 @@ enum rw_stream_flags {
      * RW_JIT_OFF or without hipRTC the generic kernel runs (rw_info.build_kind == 0); from 4096 envs on (or with RW_JIT_FORCE) rw_create
      * compiles an exact-shape packed build through hipRTC at construction (seconds; cached on disk as described at RW_JIT_OFF; rw_info.jit
      * says which happened).  RW_PIPE_ON | RW_OBS_PACKED: the classic kernel runs and rw_jit_log() says so. */
-    RW_OBS_PACKED = 1024
+    RW_OBS_PACKED = 1024,
+    /* Per-episode return and length, kept on the device (what Gymnasium's RecordEpisodeStatistics keeps on the host; the reference has no
+     * counterpart, its `info` is {}).  With RW_EPISODES_ON the engine keeps RW_BUF_EP_RETURN .. RW_BUF_EP_COUNT (below).  Per env and step,
+     * in every launch form (rw_step*, tapes, fused rollouts, HIP graphs, rw_multi):
+     *   - a NEXT_STEP reset step (the step that consumes the pending flag: action ignored, reward 0): running return and length become 0,
+     *     nothing is recorded;
+     *   - any other step: return[e][i] += reward[e][i], length[e] += 1; if the step sets `terminated`: last_return = return, last_length =
+     *     length, count += 1, and afterwards return = 0, length = 0 — in all three autoreset modes (DISABLED: a caller that keeps stepping a
+     *     finished env gets one record per such step; SAME_STEP: the record is taken from the terminating step, before the in-step reset);
+     *   - rw_reset, masked or not: running return and length of the reset envs become 0; last_* and count are untouched.
+     * rw_write seeds or zeroes all five, snapshots carry them.  Rewards are multiples of 0.5 (rware/warehouse.py:919-927, :894), so the
+     * float32 sums are exact up to 2^23.  Off by default: without the flag the same kernels run and the five buffers are empty.
+     * Which kernels run with it: as for RW_STATS_ON (the same compile switch carries the code) — the generic kernel below 4096 envs, with
+     * RW_JIT_OFF or without hipRTC, else an exact-shape build compiled at construction; rw_jit_log says so.  Combines with RW_STATS_ON,
+     * RW_OBS_PACKED, msg_bits and the IMAGE types.  RW_PIPE_ON | RW_EPISODES_ON: the classic kernel runs and rw_jit_log() says so. */
+    RW_EPISODES_ON = 2048
 };
 
 /* Device buffers (all env-major, C-contiguous).  Replaces the attributes callers read off the
@@ -198,7 +216,13 @@ enum rw_buffer_kind {
     RW_BUF_OBS_PACKED = 22,  /* uint32  [B][N][PW] RW_OBS_PACKED only (empty otherwise; RW_BUF_OBS is empty then): the FLATTENED observation
                                                    as bits, PW = 1 + ceil(L / 32) words per agent — the format at RW_OBS_PACKED.  Read-only
                                                    (rw_write refuses it)                                                        */
-    RW_BUF_KIND_COUNT = 23
+    /* RW_EPISODES_ON only (empty otherwise): the semantics are at RW_EPISODES_ON.  float32 sums of multiples of 0.5: exact up to 2^23 */
+    RW_BUF_EP_RETURN = 23,       /* float32 [B][N]  running return of the current episode, per agent                                      */
+    RW_BUF_EP_LENGTH = 24,       /* int32   [B]     running length of the current episode                                                 */
+    RW_BUF_EP_LAST_RETURN = 25,  /* float32 [B][N]  return of the env's most recently finished episode                                    */
+    RW_BUF_EP_LAST_LENGTH = 26,  /* int32   [B]     its length                                                                            */
+    RW_BUF_EP_COUNT = 27,        /* int32   [B]     episodes finished since rw_create (wrapping)                                          */
+    RW_BUF_KIND_COUNT = 28
 };
 
 /* Mirrors the constructor of rware.warehouse.Warehouse (rware/warehouse.py:146-170).  The
@@ -380,7 +404,7 @@ typedef struct rw_info {
                                   same, read from the disk cache; -1: run-time specialisation was tried and is not in use (rw_jit_log) */
     int64_t engine_bytes_per_env_step; /* bytes this engine's state layout has to move per env-step: shelf shadow (1 or 2 B per
                                   cell) + packed agent records r/w + actions + queue + counters / flags + observation + rewards +
-                                  terminated (+ messages r/w, IMAGE_DICT features).  The PMC traffic of a step is checked against
+                                  terminated (+ messages r/w, IMAGE_DICT features; RW_EPISODES_ON: running return and length r/w).  The PMC traffic of a step is checked against
                                   it; bench.py prices `frac_engine` on it (<= 1 by construction)                               */
     int32_t stagger_ticks;     /* > 0: the k-th of the first eight workgroups a CU receives starts k * stagger_ticks * 10 ns late, so that
                                   the workgroups of a CU do not run their load / agent / store phases in lock-step.  rw_create's measured rule,
@@ -392,7 +416,8 @@ typedef struct rw_info {
                                   same value.  A delay, never a different result */
     int32_t pipe_envs_per_workgroup; /* != 0: rw_step* launches run the chunk-pipelined persistent build with chunks of this many envs ... */
     int32_t pipe_workgroups;         /* ... on this many persistent workgroups (rw_stream_flags RW_PIPE_ON / RW_PIPE_OFF)              */
-    int32_t stats;                   /* 1: RW_STATS_ON — RW_BUF_STAT_* are kept (was `reserved[1]`: same struct size)                 */
+    int32_t stats;                   /* a bit set: bit 0 RW_STATS_ON — RW_BUF_STAT_* are kept; bit 1 RW_EPISODES_ON — RW_BUF_EP_* are kept
+                                        (an engine with only RW_STATS_ON reads 1, as before; was `reserved[1]`: same struct size)      */
     int32_t obs_packed;              /* 1: RW_OBS_PACKED — the launches write RW_BUF_OBS_PACKED, RW_BUF_OBS is empty; engine_bytes_per_env_step
                                         prices the packed row (appended with ABI 4)                                                  */
 } rw_info;

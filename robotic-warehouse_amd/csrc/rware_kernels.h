@@ -174,6 +174,14 @@ struct Params {
     // The reference keeps none (`info` is {}, rware/warehouse.py:746-747); read only behind the flag, nullptr otherwise
     int32_t *stat_deliveries;    // [B] shelf deliveries (:907-927)
     int32_t *stat_failed_moves;  // [B] FORWARD requests the step turned into NOOP: shelf-block cancel (:843-846) + failed movers (:871-876)
+    // episode statistics (RW_EPISODES_ON; launches carry OP_FLAG_EPISODES): per env, the running return / length of the current episode and
+    // the record of the most recently finished one (ep_tick, rware_phase_goals.h).  Rewards are multiples of 0.5, so the float32 sums are
+    // exact up to 2^23.  Appended behind every field the other kernels read; read only behind the flag, nullptr otherwise
+    float *ep_return;            // [B][N] running return of the current episode
+    int32_t *ep_length;          // [B]    running length
+    float *ep_last_return;       // [B][N] return of the env's most recently finished episode
+    int32_t *ep_last_length;     // [B]    its length
+    int32_t *ep_count;           // [B]    episodes finished since rw_create (wrapping)
 };
 
 // What changes from launch to launch.  The kernel-argument segment is rewritten by the host for every
@@ -211,7 +219,8 @@ struct LaunchArgs {
 enum : int { OP_FLAG_TIMELINE = 0x100,
              OP_FLAG_STATS = 0x200,    // count deliveries / failed moves into Params::stat_* (see count_events, rware_phase_goals.h)
              OP_FLAG_PRIO = 0x400,     // raise the wavefronts' priority until the agent phases are done (see the kernel's prologue)
-             OP_FLAG_PACKED = 0x800 }; // `obs` is uint32 [B][N][PW]: store the observation bit string as bits (RW_PACKED_BUILD kernels only)
+             OP_FLAG_PACKED = 0x800,   // `obs` is uint32 [B][N][PW]: store the observation bit string as bits (RW_PACKED_BUILD kernels only)
+             OP_FLAG_EPISODES = 0x1000 }; // keep per-episode return / length in Params::ep_* (RW_STATS_BUILD kernels only; see ep_tick, rware_phase_goals.h)
 enum : int { TL_START = 0, TL_ZEROED, TL_DMA_ISSUED, TL_ENV_LOADED, TL_LOADED, TL_AGENTS, TL_RESET, TL_OBS_BITS,
              TL_OBS_STORED, TL_END,  // 10, 11: where the wavefronts ran
              TL_AG_RECORD = 12, TL_AG_CELLS, TL_AG_WINNERS, TL_AG_APPLIED, TL_AG_GOALS,  // inside the agent phases (wavefront 0)
@@ -229,7 +238,9 @@ struct LdsLayout {
     // kDirect builds the agent lanes publish them), actions, queue, highway bitmap, per-env counter records, reset mask
     int gs, ax, ay, dir, carry, deliv, act, queue, hw, dcnt, dflag, dma_end;
     int ga, zero_end;  // cleared every launch
-    int tgt, nxt, depth, win, rew, mv, msg, fx, fy, req, obits, envi, misc, total;
+    int tgt, nxt, depth, win, rew, mv, msg, fx, fy, req, obits, envi;
+    int epr, epl;  // running episode return [E][N] / length [E] (OP_FLAG_EPISODES launches only: zero dwords otherwise)
+    int misc, total;
 };
 enum : int { ENVI_STEPS = 0, ENVI_INACTIVE = 1, ENVI_RESET = 2, ENVI_DONE = 3, ENVI_SKIP = 4,
              ENVI_QDIRTY = 5,  // a request was replaced since the chunk was staged: the queue has to be written back
@@ -241,7 +252,7 @@ RW_HD int rw_up4(int x) { return (x + 3) & ~3; }
 RW_HD uint32_t rw_magic18(int d) { return d > 0 ? (uint32_t)(((1u << 18) + (uint32_t)d - 1u) / (uint32_t)d) : 0u; }
 RW_HD int rw_div18(int x, uint32_t magic) { return (int)(((uint32_t)x * magic) >> 18); }
 
-RW_HD LdsLayout make_lds_layout(int E, int N, int Q, int HW, int SW, int OW, int cell_bytes, int act_words = 1) {
+RW_HD LdsLayout make_lds_layout(int E, int N, int Q, int HW, int SW, int OW, int cell_bytes, int act_words = 1, int episodes = 0) {
     LdsLayout l;
     int o = 0;
     const int en = rw_up4(E * N);
@@ -272,6 +283,8 @@ RW_HD LdsLayout make_lds_layout(int E, int N, int Q, int HW, int SW, int OW, int
     l.req = o;    o += rw_up4(E * SW);
     l.obits = o;  o += rw_up4(E * N * OW + 4);  // one contiguous string of E*N*L bits (+ spill words)
     l.envi = o;   o += rw_up4(E * ENVI_W);
+    l.epr = o;    o += episodes ? en : 0;
+    l.epl = o;    o += episodes ? rw_up4(E) : 0;
     l.misc = o;   o += 4;
     l.total = o;
     return l;
@@ -493,6 +506,9 @@ rware_step_kernel(const Params *__restrict__ cp, RW_LAUNCH_PARAMS) {
     // of line it moved 43 of them over a register step (BASELINE config 5's kernel 62 -> 66 VGPRs, 8 -> 7 workgroups per CU; round 6).
 #if RW_STATS_BUILD
     const bool stats_on = (la.op & OP_FLAG_STATS) != 0;  // (the flag is preloaded: a scalar test where the counters are off)
+    // Episode statistics (RW_EPISODES_ON): the same switch compiles them in, a flag of their own (preloaded likewise) turns them on.  The
+    // pipelined flow does not carry them (rw_create keeps such an engine on the classic kernels).
+    const bool ep_on = !kPipe && (la.op & OP_FLAG_EPISODES) != 0;
 #else
     constexpr bool stats_on = false;
 #endif
@@ -630,7 +646,11 @@ rware_step_kernel(const Params *__restrict__ cp, RW_LAUNCH_PARAMS) {
 #endif
     RW_MARK(TL_START);
 
+#if RW_STATS_BUILD
+    const LdsLayout lo = make_lds_layout(E, N, QL, HW, SW, OW, (int)sizeof(CellT), AM, ep_on ? 1 : 0);  // (two more arrays with the episode statistics on)
+#else
     const LdsLayout lo = make_lds_layout(E, N, QL, HW, SW, OW, (int)sizeof(CellT), AM);
+#endif
     // every per-chunk array hangs off one base (PIPE: two chunk buffers of lo.total dwords each, re-bound per chunk: bind_lds)
     int32_t *sm = smem;
     CellT *s_gs = reinterpret_cast<CellT *>(smem + lo.gs);
@@ -648,6 +668,10 @@ rware_step_kernel(const Params *__restrict__ cp, RW_LAUNCH_PARAMS) {
     uint32_t *s_obits = reinterpret_cast<uint32_t *>(smem + lo.obits);
     int32_t *s_envi = smem + lo.envi;
     int32_t *s_misc = smem + lo.misc;
+#if RW_STATS_BUILD
+    float *const s_epr = reinterpret_cast<float *>(smem + lo.epr);  // (touched only with ep_on: zero dwords otherwise)
+    int32_t *const s_epl = smem + lo.epl;
+#endif
     auto bind_lds = [&](int32_t *base) RW_INLINE {
         sm = base;
         s_gs = reinterpret_cast<CellT *>(base + lo.gs);

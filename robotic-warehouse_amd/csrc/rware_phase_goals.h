@@ -80,3 +80,37 @@
             if (ev[ENVI_INACTIVE] == 0) atomicAdd(p.stat_deliveries + (e0 + e), ev[ENVI_NDELIV]);
         }
     };
+#if RW_STATS_BUILD
+    // ep_tick (RW_STATS_BUILD kernels with RW_EPISODES_ON): one step of the per-episode return / length of agent i / env e, by the ONE lane
+    // that writes that agent / env back this step — the write-back roles for the envs that stepped and stay, RS for the envs it resets.
+    // The running values live in LDS for the launch (s_epr, s_epl): add, record-and-clear, add is an ORDERED sequence, and in a fused
+    // rollout step t's write-back and step t + 1's reset path run on different wavefronts with LDS-only barriers between them — HBM would not
+    // order them, LDS does.  HBM sees the running values once, at the launch's last step (`last`).
+    //   the env stepped (not ENVI_SKIP)   ret += reward, len += 1; `terminated` set: last_* = the sums, count += 1, then both 0 — in every
+    //                                     autoreset mode (SAME_STEP: RS calls this for the env it is about to reset; s_rew still holds the
+    //                                     terminating step's rewards, ENVI_DONE its flag)
+    //   it did not (ENVI_SKIP)            a NEXT_STEP reset step or rw_reset: both 0, nothing recorded
+    // last_* and count have one writer per element for an engine's lifetime — the same lane of the same wavefront every step (the mode is
+    // fixed per engine: RS under SAME_STEP, the write-back role otherwise) — so plain stores stay in order; count is an integer atomic.
+    const bool ep_last = !kRollout || t + 1 == n_steps;
+    auto ep_tick_agent = [&](int i, const int32_t *ev) {
+        const size_t gi = (size_t)e0 * N + i;
+        float r = 0.0f;
+        if (op == OP_STEP && !ev[ENVI_SKIP]) {
+            r = s_epr[i] + s_rew[i];
+            if (ev[ENVI_DONE]) { as_global(p.ep_last_return)[gi] = r; r = 0.0f; }
+        }
+        s_epr[i] = r;
+        if (ep_last) as_global(p.ep_return)[gi] = r;
+    };
+    auto ep_tick_env = [&](int e, const int32_t *ev) {
+        const int ge = e0 + e;
+        int l = 0;
+        if (op == OP_STEP && !ev[ENVI_SKIP]) {
+            l = s_epl[e] + 1;
+            if (ev[ENVI_DONE]) { as_global(p.ep_last_length)[ge] = l; atomicAdd(p.ep_count + ge, 1); l = 0; }
+        }
+        s_epl[e] = l;
+        if (ep_last) as_global(p.ep_length)[ge] = l;
+    };
+#endif

@@ -166,6 +166,9 @@
                 f[4] = on_highway(s_ay[i] * W + s_ax[i]) ? 1.0f : 0.0f;
                 f[5] = 0.0f;
             }
+#if RW_STATS_BUILD
+            if (RW_RARE(ep_on)) ep_tick_agent(i, s_envi + e * ENVI_W);  // (SAME_STEP: the record of the terminating step first; then cleared)
+#endif
         }
         for (int e = tid; e < ne; e += T) {
             const int32_t *ev = s_envi + e * ENVI_W;
@@ -174,6 +177,9 @@
             cnt_store(e0 + e, 0, 0);  // steps 0, nothing pending, inactive 0
             term_t[e0 + e] = (uint8_t)ev[ENVI_DONE];
             as_global(p.truncated)[e0 + e] = 0;
+#if RW_STATS_BUILD
+            if (RW_RARE(ep_on)) ep_tick_env(e, ev);
+#endif
         }
         // fused rollout: a later step's write-back (another wavefront) may store need_reset = 1 for the same env — this
         // path's stores are made visible first (vmcnt drained before the barrier; the path is rare, the wait is free)

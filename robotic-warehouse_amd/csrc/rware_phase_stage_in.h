@@ -215,6 +215,15 @@
     if constexpr (Cfg::kQrt) keep_sgpr(Q);
     RW_MARK(TL_LOADED);
     }
+#if RW_STATS_BUILD
+    // Episode statistics: the running return and length of the chunk's envs are carried like the rest of the env state — staged into LDS
+    // here (plain loads behind the stage-in barrier; their first reader runs behind the agent-phase barrier), updated there by the lane
+    // that owns the agent / env in a step's write-back or reset path (ep_tick), and stored by the launch's last step.
+    if (RW_RARE(ep_on) && op != OP_OBS) {
+        for (int i = tid; i < nea; i += T) s_epr[i] = as_global(p.ep_return)[(size_t)e0 * N + i];
+        for (int e = tid; e < ne; e += T) s_epl[e] = as_global(p.ep_length)[e0 + e];
+    }
+#endif
 
     // kRollout == false is the single-step kernel (rw_step / rw_reset / rw_refresh_obs): no loop at all.
     const int n_steps = (kRollout && op == OP_STEP) ? la.n_steps : 1;

@@ -32,6 +32,9 @@
                     // (DESIGN.md ablations).
                     if (ev[ENVI_QDIRTY])
                         for (int k = 0; k < Q; ++k) q_queue[(size_t)ge * Q + k] = s_queue[e * Q + k];
+#if RW_STATS_BUILD
+                    if (RW_RARE(ep_on)) ep_tick_env(e, ev);
+#endif
                 }
         } else if (role == 1) {  // agent records and rewards: the chunk is contiguous in both [B][N] arrays
             if (RW_RARE(stats_on)) count_events(false, lane, 64);
@@ -42,6 +45,9 @@
                     q_rec[gi] = rec_pack(s_ay[i] * W + s_ax[i], s_dir[i], s_deliv[i], s_carry[i]);  // one store stream, not five
                     rew_t[gi] = s_rew[i];
                     if (kMsg) as_global(p.amsg)[gi] = s_msg[i];
+#if RW_STATS_BUILD
+                    if (RW_RARE(ep_on)) ep_tick_agent(i, s_envi + rw_div18(i, mN) * ENVI_W);
+#endif
                 }
         } else if (role == 2) {  // patch the shelf shadow at the two cells a LOADED mover changed
             // (The exported int32 grid, RW_BUF_GRID, is NOT patched here any more: it is rebuilt from the shadow and the agent

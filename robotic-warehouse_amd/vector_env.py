@@ -7,6 +7,8 @@ plus `num_envs`, and exposes the Gymnasium VectorEnv surface:
     obs, rewards, terminated, truncated, info   = env.step(actions)
 
 with obs float32 (B, N, L), rewards float32 (B, N), terminated/truncated bool (B,), info {}.
+`episode_stats=True` (opt-in): the engine keeps per-episode return and length on the device — `env.episode_stats()`; with numpy output
+step()'s info carries Gymnasium's "episode" / "_episode" keys on the steps that finish an episode.
 `obs_format="packed"` (opt-in, FLATTENED only): obs is uint32 (B, N, PW) instead — the same observation as bits, 16 bytes per agent
 at sensor_range 1 — and `env.unpack_obs(obs)` gives the float32 form back bit for bit (packing.py has the format).
 `obs[:, i, :]` is agent i's FLATTENED observation, i.e. element i of the reference's obs tuple
@@ -151,7 +153,7 @@ class WarehouseVecEnv(_VectorEnvBase):
                  autoreset_mode: str = "next_step", devices=None, output: str = "numpy",
                  envs_per_workgroup: int = 0, threads_per_workgroup: int = 0, library: str | None = None,
                  obs_stores: str | None = None, jit=None, pipe=None, stats: bool = False, wave_priority=None,
-                 obs_format: str = "float32"):
+                 obs_format: str = "float32", episode_stats: bool = False):
         if obs_format not in ("float32", "packed"):
             raise ValueError('obs_format must be "float32" or "packed"')
         if not 0 <= int(msg_bits) <= 16:
@@ -252,7 +254,9 @@ class WarehouseVecEnv(_VectorEnvBase):
                 # in front of their first observation store at raised wavefront priority (RW_PRIO_OFF / RW_PRIO_ON) — a scheduling hint
                 wave_priority=wave_priority,
                 # obs_format="packed": RW_OBS_PACKED (the engine refuses the IMAGE types with it)
-                obs_packed=self._packed))
+                obs_packed=self._packed,
+                # True: the engine keeps per-episode return / length on the device (RW_EPISODES_ON) — see episode_stats()
+                episodes=episode_stats))
         self._bounds = [b for b in self._bounds if b[1] > b[0]]
         self.shard_bounds = list(self._bounds)  # env range [lo, hi) of every engine / device, in order
         self.devices = devices[: len(self.engines)]
@@ -265,6 +269,7 @@ class WarehouseVecEnv(_VectorEnvBase):
         # step()'s fast path: (tensor type, dtype, shape, device, bound C function, engine handle, cached result tuple); only for
         # output="torch" envs whose results are the same zero-copy views every step and whose observation needs no host-side check
         self._has_final_obs = autoreset_mode == "same_step"
+        self._episode_stats = bool(episode_stats)
         self._fast = None
         self._fast_ok = output == "torch" and not self._dict_obs and len(devices) == 1
 
@@ -441,6 +446,10 @@ class WarehouseVecEnv(_VectorEnvBase):
                 info["final_obs"] = self.dict_from_flat(info["final_obs"])
             elif want_f:  # IMAGE_DICT: the terminal observation is a dict like every other one (rware/warehouse.py:739-742)
                 info["final_obs"] = {"image": info["final_obs"], "features": self._gather("final_features")}
+        if self._episode_stats and term.any():  # Gymnasium's RecordEpisodeStatistics keys, on the steps that finish an episode only
+            done = term.view(np.bool_)
+            info = dict(info, episode={"r": np.where(done[:, None], self._gather("ep_last_return"), np.float32(0)).astype(np.float32),
+                                       "l": np.where(done, self._gather("ep_last_length"), 0).astype(np.int32)}, _episode=done.copy())
         if self._dict_obs:
             obs = self.dict_from_flat(obs)
         elif want_f:
@@ -682,6 +691,25 @@ class WarehouseVecEnv(_VectorEnvBase):
             return per_dev[0] if len(per_dev) == 1 else tuple(per_dev)
         return {k: self._gather(n) for k, n in names.items()}
 
+    EPISODE_STATS = {"return": "ep_return", "length": "ep_length", "last_return": "ep_last_return", "last_length": "ep_last_length",
+                     "count": "ep_count"}
+
+    def episode_stats(self):
+        """{"return": (B, N) float32, "length": (B,) int32, "last_return": (B, N) float32, "last_length": (B,) int32, "count": (B,) int32}
+        (`episode_stats=True` only) — per env: the running return / length of the current episode, the return / length of the most
+        recently finished one, and the number of episodes finished since construction.  Kept by the step kernels in every launch form
+        (step, rollout, capture_loop, make_pipelines), so a closed loop that never shows the host a step can still read them.  A step
+        that sets `terminated` records and clears; a NEXT_STEP reset step and reset() clear the running values only.  Rewards are
+        multiples of 0.5: the float32 sums are exact.  output="torch": zero-copy device tensors on the engine's buffers, current after
+        every launch without a copy (a tuple of dicts per device when sharded); numpy: host arrays gathered over the shards in env order."""
+        if not self._episode_stats:
+            raise RuntimeError("episode statistics are off: construct the env with episode_stats=True")
+        if self.output == "torch":
+            per_dev = [{k: self._torch.as_tensor(eng.device_array(n), device=f"cuda:{dev}") for k, n in self.EPISODE_STATS.items()}
+                       for eng, dev in zip(self.engines, self.devices)]
+            return per_dev[0] if len(per_dev) == 1 else tuple(per_dev)
+        return {k: self._gather(n) for k, n in self.EPISODE_STATS.items()}
+
     def device_tensor(self, name):
         """Zero-copy torch view of any engine buffer (single-device envs).  "obs_packed" (obs_format="packed") comes as int32 — the
         uint32 rows' bits; "obs" does not exist with that format and raises."""
@@ -698,14 +726,16 @@ class WarehouseVecEnv(_VectorEnvBase):
     # ------------------------------------------------------------------------------- state
     def get_state(self) -> dict:
         """Batched SoA state: grid (B,2,H,W), agent_* (B,N), queue (B,Q), steps/inactive (B,), rng (B,6)."""
-        out = {k: self._gather(k) for k in STATE_FIELDS + (("agent_msg",) if self.msg_bits else ())}
+        out = {k: self._gather(k) for k in STATE_FIELDS + (("agent_msg",) if self.msg_bits else ())
+               + (tuple(self.EPISODE_STATS.values()) if self._episode_stats else ())}
         out["rng"] = np.ascontiguousarray(out["rng"].T)
         return out
 
     def set_state(self, refresh_obs: bool = True, **fields):
         # `grid` first: later coordinate writes then re-mark the derived int32 view stale (layer 0 follows agent_x / agent_y)
         for k, v in sorted(fields.items(), key=lambda kv: kv[0] != "grid"):
-            if k not in STATE_FIELDS and k not in ("need_reset", "agent_msg", "stat_deliveries", "stat_failed_moves"):
+            if k not in STATE_FIELDS and k not in ("need_reset", "agent_msg", "stat_deliveries", "stat_failed_moves") \
+                    and k not in self.EPISODE_STATS.values():
                 raise KeyError(k)
             v = np.asarray(v)
             for eng, (lo, hi) in zip(self.engines, self._bounds):
