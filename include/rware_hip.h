@@ -33,7 +33,9 @@ extern "C" {
  * grows by 8 bytes), rw_unpack_obs, a 16th element (`packed`) in rw_jit_probe's shape.  Everything else is unchanged.
  * Still 4, a compatible addition: RW_EPISODES_ON in rw_stream_flags, RW_BUF_EP_RETURN .. RW_BUF_EP_COUNT appended (RW_BUF_KIND_COUNT 23 -> 28;
  * all five empty without the flag), and rw_info.stats read as a bit set — bit 0 RW_STATS_ON, bit 1 RW_EPISODES_ON — so an engine with only
- * the old flag still reports 1; rw_info keeps its size. */
+ * the old flag still reports 1; rw_info keeps its size.
+ * Still 4, a compatible addition: RW_ACTION_MASK_ON in rw_stream_flags, RW_BUF_ACTION_MASK appended (RW_BUF_KIND_COUNT 28 -> 29; empty
+ * without the flag), bit 2 of rw_info.stats; rw_info keeps its size, no new entry point. */
 #define RW_ABI_VERSION 4
 
 typedef struct rw_engine rw_engine;
@@ -163,7 +165,34 @@ enum rw_stream_flags {
      * Which kernels run with it: as for RW_STATS_ON (the same compile switch carries the code) — the generic kernel below 4096 envs, with
      * RW_JIT_OFF or without hipRTC, else an exact-shape build compiled at construction; rw_jit_log says so.  Combines with RW_STATS_ON,
      * RW_OBS_PACKED, msg_bits and the IMAGE types.  RW_PIPE_ON | RW_EPISODES_ON: the classic kernel runs and rw_jit_log() says so. */
-    RW_EPISODES_ON = 2048
+    RW_EPISODES_ON = 2048,
+    /* Per-agent valid-action masks, written by the step kernels (the reference has no counterpart, its `info` is {}; JAX ports of the
+     * environment ship one with every observation).  With RW_ACTION_MASK_ON the engine keeps RW_BUF_ACTION_MASK, uint8 [B][N]: one byte per
+     * agent, describing the state that the observation row of the same agent describes — post-step, and post-reset for envs reset in that
+     * launch.  Let t be the cell ahead of the agent along `dir`, `inside` iff t lies in the grid (Agent.req_location, rware/warehouse.py:
+     * 102-112, before clamping), and `cancel` the reference's rule at :829-844: the agent carries a shelf, and the shelf layer at t is
+     * non-zero, and NOT (an agent stands on t and that agent carries a shelf).  Then
+     *   bit 0 (NOOP), bit 2 (LEFT), bit 3 (RIGHT)   always 1;
+     *   bit 1 (FORWARD, strict)                     inside and no agent on t and not cancel;
+     *   bit 4 (TOGGLE_LOAD)                         not carrying: the shelf layer under the agent is non-zero (:889-892); carrying: the
+     *                                               agent's cell is not a highway (:893-895);
+     *   bit 5 (FORWARD_IF_VACATED)                  inside and an agent stands on t and not cancel — the move is legal if the occupant
+     *                                               leaves in the same step (a follow chain, :848-869); a permissive FORWARD mask is
+     *                                               bit 1 | bit 5;
+     *   bits 6, 7                                   0.
+     * Operationally: bit a (a = 1..4) is set iff the reference step in which this agent requests a and every other agent requests NOOP
+     * changes the agent's (x, y, dir, carrying_shelf).  With msg_bits > 0 the mask covers the Action component only.
+     * Written for every env in every autoreset mode by every launch — rw_step*, tapes, HIP graphs, rw_multi, rw_reset (masked or not),
+     * rw_refresh_obs, rw_snapshot_restore: a `terminated` env under DISABLED gets the mask of its final state, an env with a pending
+     * NEXT_STEP reset the mask of its current state (the next step ignores its action anyway); SAME_STEP: the mask belongs to the reset
+     * observation in RW_BUF_OBS, RW_BUF_FINAL_OBS gets none.  A fused rollout (rw_step_many*) leaves the mask of its LAST step.
+     * Read-only (rw_write refuses it).  Off by default: without the flag the same kernels run and the buffer is empty.
+     * Which kernels run with it: as for RW_STATS_ON / RW_EPISODES_ON (the same compile switch carries the code).  Combines with both, with
+     * RW_OBS_PACKED, msg_bits and the IMAGE types.  RW_PIPE_ON | RW_ACTION_MASK_ON: the classic kernel runs and rw_jit_log() says so.
+     * Out of scope: a per-step mask tape for rw_step_many_device (a fused rollout is open-loop — its actions exist before the launch, so
+     * nothing samples from those masks; the closed-loop forms, rw_step / graphs / pipelines, get a fresh mask every step) and masks in the
+     * pipelined (PIPE=1) kernels. */
+    RW_ACTION_MASK_ON = 4096
 };
 
 /* Device buffers (all env-major, C-contiguous).  Replaces the attributes callers read off the
@@ -222,7 +251,9 @@ enum rw_buffer_kind {
     RW_BUF_EP_LAST_RETURN = 25,  /* float32 [B][N]  return of the env's most recently finished episode                                    */
     RW_BUF_EP_LAST_LENGTH = 26,  /* int32   [B]     its length                                                                            */
     RW_BUF_EP_COUNT = 27,        /* int32   [B]     episodes finished since rw_create (wrapping)                                          */
-    RW_BUF_KIND_COUNT = 28
+    RW_BUF_ACTION_MASK = 28,     /* uint8   [B][N]  RW_ACTION_MASK_ON only (empty otherwise): the valid-action byte per agent — the bits are
+                                                    at RW_ACTION_MASK_ON.  Read-only (rw_write refuses it)                                */
+    RW_BUF_KIND_COUNT = 29
 };
 
 /* Mirrors the constructor of rware.warehouse.Warehouse (rware/warehouse.py:146-170).  The
@@ -404,7 +435,7 @@ typedef struct rw_info {
                                   same, read from the disk cache; -1: run-time specialisation was tried and is not in use (rw_jit_log) */
     int64_t engine_bytes_per_env_step; /* bytes this engine's state layout has to move per env-step: shelf shadow (1 or 2 B per
                                   cell) + packed agent records r/w + actions + queue + counters / flags + observation + rewards +
-                                  terminated (+ messages r/w, IMAGE_DICT features; RW_EPISODES_ON: running return and length r/w).  The PMC traffic of a step is checked against
+                                  terminated (+ messages r/w, IMAGE_DICT features; RW_EPISODES_ON: running return and length r/w; RW_ACTION_MASK_ON: N bytes).  The PMC traffic of a step is checked against
                                   it; bench.py prices `frac_engine` on it (<= 1 by construction)                               */
     int32_t stagger_ticks;     /* > 0: the k-th of the first eight workgroups a CU receives starts k * stagger_ticks * 10 ns late, so that
                                   the workgroups of a CU do not run their load / agent / store phases in lock-step.  rw_create's measured rule,
@@ -416,7 +447,7 @@ typedef struct rw_info {
                                   same value.  A delay, never a different result */
     int32_t pipe_envs_per_workgroup; /* != 0: rw_step* launches run the chunk-pipelined persistent build with chunks of this many envs ... */
     int32_t pipe_workgroups;         /* ... on this many persistent workgroups (rw_stream_flags RW_PIPE_ON / RW_PIPE_OFF)              */
-    int32_t stats;                   /* a bit set: bit 0 RW_STATS_ON — RW_BUF_STAT_* are kept; bit 1 RW_EPISODES_ON — RW_BUF_EP_* are kept
+    int32_t stats;                   /* a bit set: bit 0 RW_STATS_ON — RW_BUF_STAT_* are kept; bit 1 RW_EPISODES_ON — RW_BUF_EP_* are kept; bit 2 RW_ACTION_MASK_ON — RW_BUF_ACTION_MASK is written
                                         (an engine with only RW_STATS_ON reads 1, as before; was `reserved[1]`: same struct size)      */
     int32_t obs_packed;              /* 1: RW_OBS_PACKED — the launches write RW_BUF_OBS_PACKED, RW_BUF_OBS is empty; engine_bytes_per_env_step
                                         prices the packed row (appended with ABI 4)                                                  */

@@ -23,11 +23,12 @@ BUF = {
     "stat_deliveries": 20, "stat_failed_moves": 21,  # RW_STATS_ON only (empty otherwise)
     "obs_packed": 22,  # RW_OBS_PACKED only (empty otherwise; "obs" is empty then)
     "ep_return": 23, "ep_length": 24, "ep_last_return": 25, "ep_last_length": 26, "ep_count": 27,  # RW_EPISODES_ON only (empty otherwise)
+    "action_mask": 28,  # RW_ACTION_MASK_ON only (empty otherwise); read-only
 }
 BUF_DTYPE = {
     "obs": np.float32, "rewards": np.float32, "terminated": np.uint8, "truncated": np.uint8,
     "rng": np.uint64, "need_reset": np.uint8, "features": np.float32, "final_obs": np.float32, "final_features": np.float32,
-    "obs_packed": np.uint32, "ep_return": np.float32, "ep_last_return": np.float32,
+    "obs_packed": np.uint32, "ep_return": np.float32, "ep_last_return": np.float32, "action_mask": np.uint8,
 }
 
 RW_STREAM_USE_GIVEN = 1  # rw_stream_flags: `stream` is taken literally, NULL == the device's default stream
@@ -37,6 +38,7 @@ RW_PIPE_OFF, RW_PIPE_ON = 32, 64  # rw_stream_flags: the chunk-pipelined persist
 RW_PRIO_OFF, RW_PRIO_ON = 256, 512  # rw_stream_flags: raised wavefront priority on the chain in front of the first store never / always; default: the engine's measured rule
 RW_OBS_PACKED = 1024  # rw_stream_flags: bit-packed FLATTENED observations — uint32 (B, N, PW) in "obs_packed", no float32 "obs" buffer
 RW_EPISODES_ON = 2048  # rw_stream_flags: keep per-episode return / length on the device, RW_BUF_EP_RETURN .. _EP_COUNT (off by default)
+RW_ACTION_MASK_ON = 4096  # rw_stream_flags: the step kernels write a valid-action byte per agent to RW_BUF_ACTION_MASK (off by default)
 RW_STATS_ON = 128  # rw_stream_flags: keep the per-env event counters RW_BUF_STAT_DELIVERIES / _FAILED_MOVES (off by default)
 
 AUTORESET = {"disabled": 0, None: 0, "next_step": 1, "same_step": 2}
@@ -194,7 +196,7 @@ class Engine:
                  max_inactivity_steps, max_steps, reward_type, normalised_coordinates=False,
                  autoreset_mode="next_step", device_id=0, envs_per_workgroup=0,
                  threads_per_workgroup=0, stream=None, library=None, observation_type=1,
-                 image_layers=(), image_directional=True, msg_bits=0, use_given_stream=False, obs_stores=None, jit=None, pipe=None, stats=False, wave_priority=None, obs_packed=False, episodes=False):
+                 image_layers=(), image_directional=True, msg_bits=0, use_given_stream=False, obs_stores=None, jit=None, pipe=None, stats=False, wave_priority=None, obs_packed=False, episodes=False, action_mask=False):
         self.lib = load(library)
         self._h = C.c_void_p()
         self._arena, self.arena_allocations = {}, 0  # rollout_host's device tapes (grow-only; freed in close())
@@ -211,6 +213,7 @@ class Engine:
             | {None: 0, "auto": 0, False: RW_JIT_OFF, "off": RW_JIT_OFF, True: RW_JIT_FORCE, "force": RW_JIT_FORCE}[jit]
             | {None: 0, "auto": 0, False: RW_PIPE_OFF, "off": RW_PIPE_OFF, True: RW_PIPE_ON, "on": RW_PIPE_ON}[pipe]
             | (RW_STATS_ON if stats else 0) | (RW_OBS_PACKED if obs_packed else 0) | (RW_EPISODES_ON if episodes else 0)
+            | (RW_ACTION_MASK_ON if action_mask else 0)
             | {None: 0, "auto": 0, False: RW_PRIO_OFF, "off": RW_PRIO_OFF, True: RW_PRIO_ON, "on": RW_PRIO_ON}[wave_priority],
             hw.ctypes.data, goals.ctypes.data, C.c_void_p(stream or 0))
         rc = self.lib.rw_create(C.byref(cfg), C.byref(self._h))
@@ -234,10 +237,11 @@ class Engine:
             "actions": (self.B, self.N, 1 + self.M) if self.M else (self.B, self.N), "agent_msg": (self.B, self.N),
             "stat_deliveries": (self.B,), "stat_failed_moves": (self.B,),
             "ep_return": (self.B, self.N), "ep_length": (self.B,), "ep_last_return": (self.B, self.N), "ep_last_length": (self.B,),
-            "ep_count": (self.B,),
+            "ep_count": (self.B,), "action_mask": (self.B, self.N),
         }
         self.stats = bool(i.stats & 1)      # rw_info.stats is a bit set: bit 0 RW_STATS_ON, bit 1 RW_EPISODES_ON
         self.episodes = bool(i.stats & 2)
+        self.action_mask = bool(i.stats & 4)  # bit 2 RW_ACTION_MASK_ON
         # obs_packed=True (RW_OBS_PACKED): the launches write uint32 rows of PW words to "obs_packed"; "obs" does not exist
         self.packed = bool(i.obs_packed)
         self.PW = 1 + (self.L + 31) // 32 if int(observation_type) == 1 else 0

@@ -103,6 +103,7 @@ struct rw_engine {
     bool image = false;        // IMAGE / IMAGE_DICT observation kernels
     bool stats = false;        // RW_STATS_ON: every launch carries OP_FLAG_STATS, RW_BUF_STAT_* are allocated
     bool episodes = false;     // RW_EPISODES_ON: every launch carries OP_FLAG_EPISODES, RW_BUF_EP_* are allocated, the workgroups hold two more LDS arrays
+    bool mask = false;         // RW_ACTION_MASK_ON: every launch carries OP_FLAG_MASK and writes RW_BUF_ACTION_MASK (one byte per agent)
     bool packed = false;       // RW_OBS_PACKED: every launch carries OP_FLAG_PACKED and writes uint32 rows to RW_BUF_OBS_PACKED; RW_BUF_OBS is empty
     int PW = 0;                // words of a packed row, 1 + ceil(L / 32) (FLATTENED; 0 for the IMAGE types)
     int row_words = 0;         // dwords per agent of the observation the launches write: L floats, or PW words when packed
@@ -222,6 +223,7 @@ int launch(rw_engine *eng, rw::LaunchArgs la, int op, bool rollout = false, hipE
     if (!pipe) la.op |= (k.stagger_ticks & 0xff) << 16 | (k.stagger_shift & 0xf) << 24;
     if (eng->stats) la.op |= rw::OP_FLAG_STATS;
     if (eng->episodes) la.op |= rw::OP_FLAG_EPISODES;
+    if (eng->mask) la.op |= rw::OP_FLAG_MASK;
     if (eng->packed) la.op |= rw::OP_FLAG_PACKED;
     if (k.prio) la.op |= rw::OP_FLAG_PRIO;
     if (op != rw::OP_OBS) eng->grid_stale = eng->agents_stale = eng->counters_stale = true;  // the kernels keep the shadow and the packed agent records current, not the int32 views
@@ -350,7 +352,7 @@ size_t elem_size(int kind) {
         case RW_BUF_OBS: case RW_BUF_REWARDS: case RW_BUF_FEATURES: case RW_BUF_FINAL_OBS: case RW_BUF_FINAL_FEATURES: return 4;
         case RW_BUF_EP_RETURN: case RW_BUF_EP_LAST_RETURN: return 4;  // float32
         case RW_BUF_OBS_PACKED: return 4;  // uint32 words
-        case RW_BUF_TERMINATED: case RW_BUF_TRUNCATED: case RW_BUF_NEED_RESET: return 1;
+        case RW_BUF_TERMINATED: case RW_BUF_TRUNCATED: case RW_BUF_NEED_RESET: case RW_BUF_ACTION_MASK: return 1;
         case RW_BUF_RNG: return 8;
         default: return 4;
     }
@@ -465,6 +467,7 @@ int init_engine(rw_engine *eng, const rw_config *cfg, const Shape &s) {
     eng->OW = s.OW;
     eng->stats = (cfg->stream_flags & RW_STATS_ON) != 0;
     eng->episodes = s.episodes;
+    eng->mask = (cfg->stream_flags & RW_ACTION_MASK_ON) != 0;
     eng->packed = s.packed;
     eng->PW = s.PW;
     eng->row_words = s.row_words();
@@ -608,10 +611,12 @@ void pick_static(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *b)
     // event counters (RW_STATS_ON): only kernels compiled with the counting code (RW_STATS_BUILD) will do — the generic ones, a run-time
     // compiled exact-shape build (try_jit_build), and — in a library whose specialised builds were made with the switch — those
     // (RW_EPISODES_ON: the episode statistics live behind the same compile switch and take the same road)
-    if (best && (eng->stats || eng->episodes) && !rw_tab::static_has_stats()) {
+    // (RW_ACTION_MASK_ON: the valid-action masks likewise)
+    if (best && (eng->stats || eng->episodes || eng->mask) && !rw_tab::static_has_stats()) {
         best = nullptr;
         eng->jit_log = eng->stats ? "event counters: the ahead-of-time exact-shape builds do not carry the counting code"
-                                  : "episode statistics: the ahead-of-time exact-shape builds do not carry the code (RW_STATS_BUILD)";
+                     : eng->episodes ? "episode statistics: the ahead-of-time exact-shape builds do not carry the code (RW_STATS_BUILD)"
+                                     : "action masks: the ahead-of-time exact-shape builds do not carry the code (RW_STATS_BUILD)";
     }
     // packed observation rows (RW_OBS_PACKED): never an ahead-of-time specialised build — the generic kernel, or a run-time compiled
     // exact-shape build made with RW_PACKED_BUILD (try_jit_build)
@@ -649,8 +654,9 @@ int pick_build(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *b) {
     // x / N == (x * ceil(2^18 / N)) >> 18 needs x * N < 2^18 for every x < E * N
     if ((long long)E * s.N * s.N >= (1 << 18))
         return fail(eng, RW_ERR_INVALID_ARG, "envs_per_workgroup %d too large for N=%d Q=%d", E, s.N, s.Q);
-    if ((eng->stats || eng->episodes) && !rw_tab::generic_has_stats())
-        return fail(eng, RW_ERR_UNSUPPORTED, "%s: this library was built without the event-counter code (RW_STATS_BUILD)", eng->stats ? "RW_STATS_ON" : "RW_EPISODES_ON");
+    if ((eng->stats || eng->episodes || eng->mask) && !rw_tab::generic_has_stats())
+        return fail(eng, RW_ERR_UNSUPPORTED, "%s: this library was built without the event-counter code (RW_STATS_BUILD)",
+                    eng->stats ? "RW_STATS_ON" : eng->episodes ? "RW_EPISODES_ON" : "RW_ACTION_MASK_ON");
     if (eng->packed && !rw_tab::generic_has_packed())
         return fail(eng, RW_ERR_UNSUPPORTED, "RW_OBS_PACKED: this library was built without the packed observation rows (RW_PACKED_BUILD)");
     using pick_t = step_kernel_t (*)(bool, bool, bool, bool);
@@ -706,7 +712,7 @@ void try_jit_build(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *
     sh.directional = s.image ? (cfg->image_directional ? 1 : 0) : -1;
     sh.layers = s.image ? s.packed_layers() : 0;
     sh.nt = nt_rule(cfg, s, je) ? 1 : 0;
-    sh.stats = (eng->stats || eng->episodes) ? 1 : 0;  // (one compile switch, RW_STATS_BUILD, carries both)
+    sh.stats = (eng->stats || eng->episodes || eng->mask) ? 1 : 0;  // (one compile switch, RW_STATS_BUILD, carries all three)
     sh.packed = eng->packed ? 1 : 0;
     // (two attempts: a CACHED code object the runtime refuses — a truncated or foreign file behind a well-formed header — is
     //  dropped from the cache and the shape compiled afresh, once; otherwise every later construction would trip over it)
@@ -835,7 +841,7 @@ void pick_pipe(rw_engine *eng, const rw_config *cfg, const Shape &s) {
     const char *pee = rw_hook("RWARE_PIPE_E");
     const int want_e = pee ? atoi(pee) : 0;
     const StaticEntry *pb = nullptr;
-    if (mode >= 0 && !s.image && s.M == 0 && !eng->step.jit && !(eng->stats && !rw_tab::static_has_stats()) && !eng->packed && !eng->episodes)
+    if (mode >= 0 && !s.image && s.M == 0 && !eng->step.jit && !(eng->stats && !rw_tab::static_has_stats()) && !eng->packed && !eng->episodes && !eng->mask)
         pb = find_static([&](const StaticEntry &se) { return se.pipe && se.N == s.N && serves(se, s) && (!want_e || se.E == want_e); });
     if (pb) {
         const int n_cu = eng->prop.multiProcessorCount;
@@ -867,6 +873,7 @@ void pick_pipe(rw_engine *eng, const rw_config *cfg, const Shape &s) {
         eng->jit_log += "pipe: RW_PIPE_ON requested, the classic kernel runs: ";
         if (eng->packed) eng->jit_log += "packed observations (RW_OBS_PACKED) are served by the classic kernels only";
         else if (eng->episodes) eng->jit_log += "episode statistics (RW_EPISODES_ON) are served by the classic kernels only";
+        else if (eng->mask) eng->jit_log += "action masks (RW_ACTION_MASK_ON) are served by the classic kernels only";
         else
 #if RW_WITH_PIPE
         eng->jit_log += pb ? "the pipelined build of this shape does not fit (LDS / occupancy)"
@@ -907,6 +914,8 @@ int alloc_state(rw_engine *eng, const rw_config *cfg, const Shape &s) {
     // the episode statistics: likewise
     n_elems[RW_BUF_EP_RETURN] = n_elems[RW_BUF_EP_LAST_RETURN] = eng->episodes ? szB * N : 0;
     n_elems[RW_BUF_EP_LENGTH] = n_elems[RW_BUF_EP_LAST_LENGTH] = n_elems[RW_BUF_EP_COUNT] = eng->episodes ? szB : 0;
+    // the valid-action masks: likewise (an output, one byte per agent)
+    n_elems[RW_BUF_ACTION_MASK] = eng->mask ? szB * N : 0;
     // One slab for every buffer: the per-step working set (agent SoA, queue, counters, flags, rewards,
     // shelf shadow) sits in a few contiguous MiB, so a workgroup's ~15 streams share TLB entries
     // instead of touching 15 separate allocations.  Order = hot and small first.
@@ -914,7 +923,7 @@ int alloc_state(rw_engine *eng, const rw_config *cfg, const Shape &s) {
         RW_BUF_AGENT_X, RW_BUF_AGENT_Y, RW_BUF_AGENT_DIR, RW_BUF_AGENT_CARRY, RW_BUF_AGENT_DELIVERED, RW_BUF_QUEUE,
         RW_BUF_AGENT_MSG, RW_BUF_STEPS, RW_BUF_INACTIVE, RW_BUF_NEED_RESET, RW_BUF_REWARDS, RW_BUF_TERMINATED, RW_BUF_TRUNCATED,
         RW_BUF_STAT_DELIVERIES, RW_BUF_STAT_FAILED_MOVES, RW_BUF_EP_RETURN, RW_BUF_EP_LENGTH, RW_BUF_EP_LAST_RETURN, RW_BUF_EP_LAST_LENGTH,
-        RW_BUF_EP_COUNT, RW_BUF_ACTIONS, RW_BUF_RNG, RW_BUF_FEATURES, RW_BUF_OBS, RW_BUF_OBS_PACKED, RW_BUF_FINAL_OBS, RW_BUF_FINAL_FEATURES, RW_BUF_GRID};
+        RW_BUF_EP_COUNT, RW_BUF_ACTION_MASK, RW_BUF_ACTIONS, RW_BUF_RNG, RW_BUF_FEATURES, RW_BUF_OBS, RW_BUF_OBS_PACKED, RW_BUF_FINAL_OBS, RW_BUF_FINAL_FEATURES, RW_BUF_GRID};
     auto up = [](size_t x) { return (x + 4095) & ~(size_t)4095; };
     size_t slab_bytes = 0, off[RW_BUF_KIND_COUNT];
     eng->rec_off = 0;  // the packed agent records lead the hot set, the counter records follow
@@ -1013,6 +1022,7 @@ int fill_params(rw_engine *eng, const rw_config *cfg, const Shape &s) {
     p.ep_last_return = eng->episodes ? (float *)eng->buf[RW_BUF_EP_LAST_RETURN].ptr : nullptr;
     p.ep_last_length = eng->episodes ? (int32_t *)eng->buf[RW_BUF_EP_LAST_LENGTH].ptr : nullptr;
     p.ep_count = eng->episodes ? (int32_t *)eng->buf[RW_BUF_EP_COUNT].ptr : nullptr;
+    p.action_mask = eng->mask ? (uint8_t *)eng->buf[RW_BUF_ACTION_MASK].ptr : nullptr;
     rw::LaunchArgs &la = eng->la;
     la.actions = (const int32_t *)eng->buf[RW_BUF_ACTIONS].ptr;
     la.reset_mask = eng->d_mask;
@@ -1532,6 +1542,8 @@ int rw_write(rw_engine *eng, int kind, const void *host_src, size_t bytes) {
     // would stick for the engine's lifetime — refused rather than silently different from the reference
     if (kind == RW_BUF_OBS_PACKED)
         return fail(eng, RW_ERR_INVALID_ARG, "rw_write: RW_BUF_OBS_PACKED is read-only (an output of the step kernels)");
+    if (kind == RW_BUF_ACTION_MASK)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_write: RW_BUF_ACTION_MASK is read-only (an output of the step kernels)");
     if (kind == RW_BUF_TRUNCATED)
         return fail(eng, RW_ERR_INVALID_ARG, "rw_write: RW_BUF_TRUNCATED is read-only (the reference never truncates, rware/warehouse.py:942)");
     RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
@@ -1594,7 +1606,7 @@ int rw_get_info(const rw_engine *eng, rw_info *out) {
     out->stagger_ticks = eng->step.stagger_ticks;
     out->pipe_envs_per_workgroup = eng->pipe.E;
     out->pipe_workgroups = eng->pipe.grid;
-    out->stats = (eng->stats ? 1 : 0) | (eng->episodes ? 2 : 0);  // (a bit set: an engine with only RW_STATS_ON still reads 1)
+    out->stats = (eng->stats ? 1 : 0) | (eng->episodes ? 2 : 0) | (eng->mask ? 4 : 0);  // (a bit set: an engine with only RW_STATS_ON still reads 1)
     out->obs_packed = eng->packed ? 1 : 0;
     out->wave_priority = (eng->step.prio ? 1 : 0) | (eng->rollout.prio ? 2 : 0);
     out->specialised = eng->build_kind != 0 ? 1 : 0;
@@ -1612,7 +1624,8 @@ int rw_get_info(const rw_engine *eng, rw_info *out) {
     out->engine_bytes_per_env_step =
         (int64_t)p.HW * (eng->wide ? 2 : 1) + 8LL * p.N + 4LL * p.N * (1 + eng->msg_bits) + 4LL * p.Q + 16 + 4LL * p.N * eng->row_words +
         4LL * p.N + 1 + (eng->msg_bits ? 8LL * p.N : 0) + (p.features ? 24LL * p.N : 0) +
-        (eng->episodes ? 2 * (4LL * p.N + 4) : 0);  // (RW_EPISODES_ON: the running return and length, read + write)
+        (eng->episodes ? 2 * (4LL * p.N + 4) : 0) +  // (RW_EPISODES_ON: the running return and length, read + write)
+        (eng->mask ? (int64_t)p.N : 0);               // (RW_ACTION_MASK_ON: one byte per agent, written)
     snprintf(out->device_name, sizeof out->device_name, "%s", eng->prop.name);
     snprintf(out->arch_name, sizeof out->arch_name, "%s", eng->prop.gcnArchName);
     return RW_OK;

@@ -182,6 +182,9 @@ struct Params {
     float *ep_last_return;       // [B][N] return of the env's most recently finished episode
     int32_t *ep_last_length;     // [B]    its length
     int32_t *ep_count;           // [B]    episodes finished since rw_create (wrapping)
+    // valid-action masks (RW_ACTION_MASK_ON; launches carry OP_FLAG_MASK): one byte per agent, describing the state the observation row of
+    // the same launch describes (action_mask_store, rware_phase_goals.h).  An output; read only behind the flag, nullptr otherwise
+    uint8_t *action_mask;        // [B][N] bit a = 1: action a is no certain no-op; bit 5: FORWARD_IF_VACATED
 };
 
 // What changes from launch to launch.  The kernel-argument segment is rewritten by the host for every
@@ -220,7 +223,8 @@ enum : int { OP_FLAG_TIMELINE = 0x100,
              OP_FLAG_STATS = 0x200,    // count deliveries / failed moves into Params::stat_* (see count_events, rware_phase_goals.h)
              OP_FLAG_PRIO = 0x400,     // raise the wavefronts' priority until the agent phases are done (see the kernel's prologue)
              OP_FLAG_PACKED = 0x800,   // `obs` is uint32 [B][N][PW]: store the observation bit string as bits (RW_PACKED_BUILD kernels only)
-             OP_FLAG_EPISODES = 0x1000 }; // keep per-episode return / length in Params::ep_* (RW_STATS_BUILD kernels only; see ep_tick, rware_phase_goals.h)
+             OP_FLAG_EPISODES = 0x1000, // keep per-episode return / length in Params::ep_* (RW_STATS_BUILD kernels only; see ep_tick, rware_phase_goals.h)
+             OP_FLAG_MASK = 0x2000 };   // write the per-agent valid-action bytes to Params::action_mask (RW_STATS_BUILD kernels only; see action_mask_store, rware_phase_goals.h)
 enum : int { TL_START = 0, TL_ZEROED, TL_DMA_ISSUED, TL_ENV_LOADED, TL_LOADED, TL_AGENTS, TL_RESET, TL_OBS_BITS,
              TL_OBS_STORED, TL_END,  // 10, 11: where the wavefronts ran
              TL_AG_RECORD = 12, TL_AG_CELLS, TL_AG_WINNERS, TL_AG_APPLIED, TL_AG_GOALS,  // inside the agent phases (wavefront 0)
@@ -509,6 +513,8 @@ rware_step_kernel(const Params *__restrict__ cp, RW_LAUNCH_PARAMS) {
     // Episode statistics (RW_EPISODES_ON): the same switch compiles them in, a flag of their own (preloaded likewise) turns them on.  The
     // pipelined flow does not carry them (rw_create keeps such an engine on the classic kernels).
     const bool ep_on = !kPipe && (la.op & OP_FLAG_EPISODES) != 0;
+    // Valid-action masks (RW_ACTION_MASK_ON): likewise — the same switch, a preloaded flag of their own, not in the pipelined flow.
+    const bool mask_on = !kPipe && (la.op & OP_FLAG_MASK) != 0;
 #else
     constexpr bool stats_on = false;
 #endif

@@ -36,6 +36,14 @@
                     if (counted && (s_ax[i] >= H || s_ay[i] >= W)) atomicOr(p.status, STATUS_IMAGE_INDEX);
                 }
         }
+#if RW_STATS_BUILD
+        if (RW_RARE(mask_on))  // valid-action bytes of the envs that stay (every observation type; the envs reset in this launch: RS)
+            for (int i = lane; i < nea; i += 64) {
+                const int e = rw_div18(i, mN);
+                if (s_envi[e * ENVI_W + ENVI_RESET]) continue;
+                action_mask_store(i, e);
+            }
+#endif
     }
     // ---------------------------------------------------------------- P7: observation bits (:598-674)
     // One contiguous bit string per workgroup: bit (i*L + k) == obs[agent i][k] for k >= 2; the two

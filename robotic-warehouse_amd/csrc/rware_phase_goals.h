@@ -113,4 +113,26 @@
         s_epl[e] = l;
         if (ep_last) as_global(p.ep_length)[ge] = l;
     };
+    // action_mask_store (RW_STATS_BUILD kernels with RW_ACTION_MASK_ON): the valid-action byte of agent i of env e — the contract is at
+    // RW_ACTION_MASK_ON in include/rware_hip.h — from the state the observation of this step is built from: the agent's own record, the
+    // final per-cell layers (agent layer s_ga, shelf layer s_gs with every carried shelf under its carrier) and the highway bitmap.  Two
+    // call sites, one writer per byte and launch: OS for the envs that stay (rware_phase_gather.h), RS for the envs this launch resets
+    // (rware_phase_reset.h; OS skips those).  The occupant's load comes from its own record (s_carry), not from the agent layer's load
+    // bit, which only the IMAGE gathers depend on.  All LDS reads unconditional (an off-map cell ahead reads the agent's own cell and is
+    // masked).  Fused rollout: only the launch's last step stores (`ep_last`), nothing reads the earlier ones.
+    auto action_mask_store = [&](int i, int e) {
+        if (!ep_last) return;
+        const int x = s_ax[i], y = s_ay[i], d = s_dir[i], carry = s_carry[i];
+        const bool inside = d == DIR_UP ? y > 0 : d == DIR_DOWN ? y < H - 1 : d == DIR_LEFT ? x > 0 : x < W - 1;  // (Agent.req_location before clamping, :102-112)
+        const int own = y * W + x;
+        const int tc = e * HW + (inside ? own + (d == DIR_UP ? -W : d == DIR_DOWN ? W : d == DIR_LEFT ? -1 : 1) : own);
+        const int ga_t = s_ga[tc] & 0x7f, gs_t = (int)s_gs[tc], gs_own = (int)s_gs[e * HW + own];
+        const int occ = inside ? ga_t : 0;                        // the agent standing on the cell ahead, 1-based
+        const int occ_carry = s_carry[e * N + (occ ? occ - 1 : 0)];
+        const bool cancel = carry && gs_t != 0 && !(occ && occ_carry);  // a loaded agent in front of a standing shelf (:829-844)
+        const bool fwd = inside && !cancel;
+        const bool toggle = carry ? !on_highway(own) : gs_own != 0;    // unload off the highway (:893-895), load where a shelf stands (:889-892)
+        const uint32_t m = 1u | 4u | 8u | ((fwd && !occ) ? 2u : 0u) | (toggle ? 16u : 0u) | ((fwd && occ) ? 32u : 0u);
+        as_global(p.action_mask)[(size_t)e0 * N + i] = (uint8_t)m;
+    };
 #endif

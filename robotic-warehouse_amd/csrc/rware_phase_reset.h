@@ -168,6 +168,7 @@
             }
 #if RW_STATS_BUILD
             if (RW_RARE(ep_on)) ep_tick_agent(i, s_envi + e * ENVI_W);  // (SAME_STEP: the record of the terminating step first; then cleared)
+            if (RW_RARE(mask_on)) action_mask_store(i, e);  // (the fresh agents: the layers of the reset env are final behind the barrier above)
 #endif
         }
         for (int e = tid; e < ne; e += T) {

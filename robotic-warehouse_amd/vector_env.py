@@ -9,6 +9,8 @@ plus `num_envs`, and exposes the Gymnasium VectorEnv surface:
 with obs float32 (B, N, L), rewards float32 (B, N), terminated/truncated bool (B,), info {}.
 `episode_stats=True` (opt-in): the engine keeps per-episode return and length on the device — `env.episode_stats()`; with numpy output
 step()'s info carries Gymnasium's "episode" / "_episode" keys on the steps that finish an episode.
+`action_mask=True` (opt-in): the step kernels write a valid-action byte per agent — `env.action_mask()`, bool (B, N, 5); with numpy
+output reset() and step() add info["action_mask"].
 `obs_format="packed"` (opt-in, FLATTENED only): obs is uint32 (B, N, PW) instead — the same observation as bits, 16 bytes per agent
 at sensor_range 1 — and `env.unpack_obs(obs)` gives the float32 form back bit for bit (packing.py has the format).
 `obs[:, i, :]` is agent i's FLATTENED observation, i.e. element i of the reference's obs tuple
@@ -153,7 +155,7 @@ class WarehouseVecEnv(_VectorEnvBase):
                  autoreset_mode: str = "next_step", devices=None, output: str = "numpy",
                  envs_per_workgroup: int = 0, threads_per_workgroup: int = 0, library: str | None = None,
                  obs_stores: str | None = None, jit=None, pipe=None, stats: bool = False, wave_priority=None,
-                 obs_format: str = "float32", episode_stats: bool = False):
+                 obs_format: str = "float32", episode_stats: bool = False, action_mask: bool = False):
         if obs_format not in ("float32", "packed"):
             raise ValueError('obs_format must be "float32" or "packed"')
         if not 0 <= int(msg_bits) <= 16:
@@ -256,7 +258,9 @@ class WarehouseVecEnv(_VectorEnvBase):
                 # obs_format="packed": RW_OBS_PACKED (the engine refuses the IMAGE types with it)
                 obs_packed=self._packed,
                 # True: the engine keeps per-episode return / length on the device (RW_EPISODES_ON) — see episode_stats()
-                episodes=episode_stats))
+                episodes=episode_stats,
+                # True: the step kernels write the valid-action byte of every agent (RW_ACTION_MASK_ON) — see action_mask()
+                action_mask=action_mask))
         self._bounds = [b for b in self._bounds if b[1] > b[0]]
         self.shard_bounds = list(self._bounds)  # env range [lo, hi) of every engine / device, in order
         self.devices = devices[: len(self.engines)]
@@ -270,6 +274,7 @@ class WarehouseVecEnv(_VectorEnvBase):
         # output="torch" envs whose results are the same zero-copy views every step and whose observation needs no host-side check
         self._has_final_obs = autoreset_mode == "same_step"
         self._episode_stats = bool(episode_stats)
+        self._action_mask = bool(action_mask)
         self._fast = None
         self._fast_ok = output == "torch" and not self._dict_obs and len(devices) == 1
 
@@ -330,7 +335,7 @@ class WarehouseVecEnv(_VectorEnvBase):
         m = None if mask is None else np.asarray(mask).astype(np.uint8).reshape(self.num_envs)
         for eng, (lo, hi) in zip(self.engines, self._bounds):
             eng.reset(None if seeds is None else seeds[lo:hi], None if m is None else m[lo:hi])
-        return self._observations(), {}
+        return self._observations(), ({"action_mask": self.action_mask()} if self._action_mask and self.output != "torch" else {})
 
     def step(self, actions):
         """Warehouse.step (:804-946) for every env; actions (B, N) ints in 0..4 or Action members.
@@ -450,6 +455,8 @@ class WarehouseVecEnv(_VectorEnvBase):
             done = term.view(np.bool_)
             info = dict(info, episode={"r": np.where(done[:, None], self._gather("ep_last_return"), np.float32(0)).astype(np.float32),
                                        "l": np.where(done, self._gather("ep_last_length"), 0).astype(np.int32)}, _episode=done.copy())
+        if self._action_mask:  # the strict mask of the state `obs` describes
+            info = dict(info, action_mask=self.action_mask())
         if self._dict_obs:
             obs = self.dict_from_flat(obs)
         elif want_f:
@@ -709,6 +716,33 @@ class WarehouseVecEnv(_VectorEnvBase):
                        for eng, dev in zip(self.engines, self.devices)]
             return per_dev[0] if len(per_dev) == 1 else tuple(per_dev)
         return {k: self._gather(n) for k, n in self.EPISODE_STATS.items()}
+
+    def action_mask(self, permissive=False):
+        """bool (B, N, 5) (`action_mask=True` only): [..., a] says whether Action a can change agent's (x, y, dir, carrying_shelf) in the
+        state the current observation describes — what a masked policy multiplies its logits with.  NOOP, LEFT and RIGHT are always
+        True; FORWARD is False into a wall, into a cell an agent stands on, and for a loaded agent into a standing shelf; TOGGLE_LOAD
+        is False where there is nothing to load, and for a loaded agent on a highway.  `permissive`: FORWARD is also True where the
+        only obstacle is an agent that may leave in the same step (a follow chain; bit 5 of the raw byte) — strict never lets a legal
+        move through as a no-op, permissive never masks a move that could succeed.  Written by the step kernels in every launch form
+        (step, reset, capture_loop, make_pipelines; rollout() leaves the mask of its last step).  numpy output: a host array gathered
+        over the shards; output="torch": a device tensor computed from the zero-copy uint8 (B, N) buffer, device_tensor("action_mask")
+        (a tuple per device when sharded).  The raw byte's bits are in include/rware_hip.h at RW_ACTION_MASK_ON."""
+        if not self._action_mask:
+            raise RuntimeError("action masks are off: construct the env with action_mask=True")
+        if self.output == "torch":
+            t = self._torch
+            per_dev = []
+            for eng, dev in zip(self.engines, self.devices):
+                raw = t.as_tensor(eng.device_array("action_mask"), device=f"cuda:{dev}")
+                if permissive:
+                    raw = raw | ((raw >> 4) & 2)
+                shifts = t.arange(5, dtype=t.uint8, device=raw.device)
+                per_dev.append(((raw.unsqueeze(-1) >> shifts) & 1).to(t.bool))
+            return per_dev[0] if len(per_dev) == 1 else tuple(per_dev)
+        raw = self._gather("action_mask")
+        if permissive:
+            raw = raw | ((raw >> 4) & 2)
+        return ((raw[..., None] >> np.arange(5, dtype=np.uint8)) & 1).astype(np.bool_)
 
     def device_tensor(self, name):
         """Zero-copy torch view of any engine buffer (single-device envs).  "obs_packed" (obs_format="packed") comes as int32 — the
