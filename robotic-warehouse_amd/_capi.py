@@ -16,20 +16,36 @@ DEFAULT_LIBRARY = os.path.join(_HERE, "csrc", "librware_hip.so")
 RW_ABI_VERSION = 4
 RW_OK, RW_ERR_INVALID_ARG, RW_ERR_INVALID_ACTION, RW_ERR_HIP, RW_ERR_UNSUPPORTED, RW_ERR_NO_DEVICE, RW_ERR_INDEX, RW_ERR_SELFTEST = 0, -1, -2, -3, -4, -5, -6, -7
 
-BUF = {
-    "obs": 0, "rewards": 1, "terminated": 2, "truncated": 3, "grid": 4, "agent_x": 5, "agent_y": 6,
-    "agent_dir": 7, "agent_carry": 8, "agent_delivered": 9, "queue": 10, "steps": 11, "inactive": 12,
-    "rng": 13, "need_reset": 14, "actions": 15, "features": 16, "agent_msg": 17, "final_obs": 18, "final_features": 19,
-    "stat_deliveries": 20, "stat_failed_moves": 21,  # RW_STATS_ON only (empty otherwise)
-    "obs_packed": 22,  # RW_OBS_PACKED only (empty otherwise; "obs" is empty then)
-    "ep_return": 23, "ep_length": 24, "ep_last_return": 25, "ep_last_length": 26, "ep_count": 27,  # RW_EPISODES_ON only (empty otherwise)
-    "action_mask": 28,  # RW_ACTION_MASK_ON only (empty otherwise); read-only
+# Every RW_BUF_* kind of include/rware_hip.h, once: name -> (kind id, dtype, shape as a function of the engine's sizes, role).
+# Roles: "state" is what reset() / step() evolve and a snapshot holds, "view" a derived view of it (both writable: set_state takes
+# them), "io" the launches' inputs and outputs.  Where a kind exists only with a flag (empty otherwise) the comment names it.
+_b, _bn, _bn6, _obs = (lambda e: (e.B,)), (lambda e: (e.B, e.N)), (lambda e: (e.B, e.N, 6)), (lambda e: e.obs_shape)
+BUFFERS = {
+    "obs": (0, np.float32, _obs, "io"),  # not with RW_OBS_PACKED
+    "rewards": (1, np.float32, _bn, "io"),
+    "terminated": (2, np.uint8, _b, "io"),
+    "truncated": (3, np.uint8, _b, "io"),  # read-only
+    "grid": (4, np.int32, lambda e: (e.B, 2, e.H, e.W), "view"),
+    "agent_x": (5, np.int32, _bn, "view"), "agent_y": (6, np.int32, _bn, "view"), "agent_dir": (7, np.int32, _bn, "view"),
+    "agent_carry": (8, np.int32, _bn, "view"), "agent_delivered": (9, np.int32, _bn, "view"),
+    "queue": (10, np.int32, lambda e: (e.B, e.Q), "state"),
+    "steps": (11, np.int32, _b, "view"), "inactive": (12, np.int32, _b, "view"),
+    "rng": (13, np.uint64, lambda e: (6, e.B), "state"),
+    "need_reset": (14, np.uint8, _b, "view"),
+    "actions": (15, np.int32, lambda e: (e.B, e.N, 1 + e.M) if e.M else (e.B, e.N), "io"),
+    "features": (16, np.float32, _bn6, "io"),
+    "agent_msg": (17, np.int32, _bn, "state"),
+    "final_obs": (18, np.float32, _obs, "io"),  # SAME_STEP autoreset only
+    "final_features": (19, np.float32, _bn6, "io"),  # SAME_STEP autoreset with IMAGE_DICT only
+    "stat_deliveries": (20, np.int32, _b, "state"), "stat_failed_moves": (21, np.int32, _b, "state"),  # RW_STATS_ON only
+    "obs_packed": (22, np.uint32, lambda e: (e.B, e.N, e.PW), "io"),  # RW_OBS_PACKED only; read-only
+    "ep_return": (23, np.float32, _bn, "state"), "ep_length": (24, np.int32, _b, "state"),  # RW_EPISODES_ON only (these five)
+    "ep_last_return": (25, np.float32, _bn, "state"), "ep_last_length": (26, np.int32, _b, "state"), "ep_count": (27, np.int32, _b, "state"),
+    "action_mask": (28, np.uint8, _bn, "io"),  # RW_ACTION_MASK_ON only; read-only
 }
-BUF_DTYPE = {
-    "obs": np.float32, "rewards": np.float32, "terminated": np.uint8, "truncated": np.uint8,
-    "rng": np.uint64, "need_reset": np.uint8, "features": np.float32, "final_obs": np.float32, "final_features": np.float32,
-    "obs_packed": np.uint32, "ep_return": np.float32, "ep_last_return": np.float32, "action_mask": np.uint8,
-}
+BUF = {name: row[0] for name, row in BUFFERS.items()}
+BUF_DTYPE = {name: row[1] for name, row in BUFFERS.items()}
+WRITABLE_STATE = tuple(name for name, row in BUFFERS.items() if row[3] != "io")  # what WarehouseVecEnv.set_state accepts
 
 RW_STREAM_USE_GIVEN = 1  # rw_stream_flags: `stream` is taken literally, NULL == the device's default stream
 RW_OBS_STORES_CACHED, RW_OBS_STORES_STREAM = 2, 4  # rw_stream_flags: keep the observation lines cached / force the non-temporal hint
@@ -226,26 +242,14 @@ class Engine:
         self.H, self.W = i.grid_h, i.grid_w
         self.M = int(msg_bits)
         win = 2 * int(sensor_range) + 1
-        obs_shape = (self.B, self.N, self.L) if int(observation_type) == 1 else (self.B, self.N, self.L // (win * win), win, win)
-        self.shapes = {
-            "features": (self.B, self.N, 6), "final_features": (self.B, self.N, 6),
-            "obs": obs_shape, "final_obs": obs_shape, "rewards": (self.B, self.N), "terminated": (self.B,),
-            "truncated": (self.B,), "grid": (self.B, 2, self.H, self.W), "agent_x": (self.B, self.N),
-            "agent_y": (self.B, self.N), "agent_dir": (self.B, self.N), "agent_carry": (self.B, self.N),
-            "agent_delivered": (self.B, self.N), "queue": (self.B, self.Q), "steps": (self.B,),
-            "inactive": (self.B,), "rng": (6, self.B), "need_reset": (self.B,),
-            "actions": (self.B, self.N, 1 + self.M) if self.M else (self.B, self.N), "agent_msg": (self.B, self.N),
-            "stat_deliveries": (self.B,), "stat_failed_moves": (self.B,),
-            "ep_return": (self.B, self.N), "ep_length": (self.B,), "ep_last_return": (self.B, self.N), "ep_last_length": (self.B,),
-            "ep_count": (self.B,), "action_mask": (self.B, self.N),
-        }
+        self.obs_shape = (self.B, self.N, self.L) if int(observation_type) == 1 else (self.B, self.N, self.L // (win * win), win, win)
+        self.PW = 1 + (self.L + 31) // 32 if int(observation_type) == 1 else 0  # words of a packed row (FLATTENED)
+        self.shapes = {name: row[2](self) for name, row in BUFFERS.items()}
         self.stats = bool(i.stats & 1)      # rw_info.stats is a bit set: bit 0 RW_STATS_ON, bit 1 RW_EPISODES_ON
         self.episodes = bool(i.stats & 2)
         self.action_mask = bool(i.stats & 4)  # bit 2 RW_ACTION_MASK_ON
         # obs_packed=True (RW_OBS_PACKED): the launches write uint32 rows of PW words to "obs_packed"; "obs" does not exist
         self.packed = bool(i.obs_packed)
-        self.PW = 1 + (self.L + 31) // 32 if int(observation_type) == 1 else 0
-        self.shapes["obs_packed"] = (self.B, self.N, self.PW)
         self.obs_name = "obs_packed" if self.packed else "obs"  # the observation buffer the launches write
 
     def _check(self, rc):
@@ -376,7 +380,7 @@ class Engine:
 
     # buffers ------------------------------------------------------------------------------
     def read(self, name) -> np.ndarray:
-        out = np.empty(self.shapes[name], dtype=BUF_DTYPE.get(name, np.int32))
+        out = np.empty(self.shapes[name], dtype=BUF_DTYPE[name])
         self._check(self.lib.rw_read(self._h, BUF[name], out.ctypes.data, out.nbytes))
         return out
 
@@ -393,7 +397,7 @@ class Engine:
         return obs, rew, term, feat
 
     def write(self, name, array):
-        a = np.ascontiguousarray(array, dtype=BUF_DTYPE.get(name, np.int32)).reshape(self.shapes[name])
+        a = np.ascontiguousarray(array, dtype=BUF_DTYPE[name]).reshape(self.shapes[name])
         self._check(self.lib.rw_write(self._h, BUF[name], a.ctypes.data, a.nbytes))
 
     def unpack_obs_device(self, packed_ptr, out_ptr, n_rows):
@@ -407,7 +411,7 @@ class Engine:
         if name in ("obs", "obs_packed") and not nbytes.value:
             raise RuntimeError('this engine writes packed observations (obs_format="packed"): there is no float32 "obs" buffer — use "obs_packed" and unpack_obs'
                                if name == "obs" else 'this engine writes float32 observations: "obs_packed" exists only with obs_format="packed"')
-        return DeviceArray(ptr.value or 0, self.shapes[name], dtype or BUF_DTYPE.get(name, np.int32), self)
+        return DeviceArray(ptr.value or 0, self.shapes[name], dtype or BUF_DTYPE[name], self)
 
     def recalc_grid(self, shelf_xy):
         s = np.ascontiguousarray(shelf_xy, dtype=np.int32).reshape(self.B, -1, 2)

@@ -683,6 +683,18 @@ class WarehouseVecEnv(_VectorEnvBase):
             self._tviews[d] = v
         return v
 
+    def _per_device(self, make):
+        """output="torch": make(view) once per device, `view(name)` being the zero-copy tensor of that device's engine buffer `name` — the
+        result itself for a single device, a tuple of them (shard order) when sharded."""
+        per_dev = [make(lambda name: self._torch.as_tensor(eng.device_array(name), device=f"cuda:{dev}"))
+                   for eng, dev in zip(self.engines, self.devices)]
+        return per_dev[0] if len(per_dev) == 1 else tuple(per_dev)
+
+    def _named_buffers(self, names):
+        """{key: buffer `names[key]`}: zero-copy device tensors (output="torch", _per_device) or host arrays gathered over the shards."""
+        make = lambda view: {k: view(n) for k, n in names.items()}
+        return self._per_device(make) if self.output == "torch" else make(self._gather)
+
     def event_counters(self):
         """{"deliveries": (B,), "failed_moves": (B,)} int32 — running totals per env since construction (`stats=True` only; the
         engine never resets them: an episode's figure is the difference between two reads).  deliveries: requested shelves brought
@@ -691,12 +703,7 @@ class WarehouseVecEnv(_VectorEnvBase):
         is {} (:746-747), and so is this env's.  output="torch": zero-copy device tensors (a tuple per device when sharded)."""
         if not self.engines[0].stats:
             raise RuntimeError("event counters are off: construct the env with stats=True")
-        names = {"deliveries": "stat_deliveries", "failed_moves": "stat_failed_moves"}
-        if self.output == "torch":
-            per_dev = [{k: self._torch.as_tensor(eng.device_array(n), device=f"cuda:{dev}") for k, n in names.items()}
-                       for eng, dev in zip(self.engines, self.devices)]
-            return per_dev[0] if len(per_dev) == 1 else tuple(per_dev)
-        return {k: self._gather(n) for k, n in names.items()}
+        return self._named_buffers({"deliveries": "stat_deliveries", "failed_moves": "stat_failed_moves"})
 
     EPISODE_STATS = {"return": "ep_return", "length": "ep_length", "last_return": "ep_last_return", "last_length": "ep_last_length",
                      "count": "ep_count"}
@@ -711,11 +718,7 @@ class WarehouseVecEnv(_VectorEnvBase):
         every launch without a copy (a tuple of dicts per device when sharded); numpy: host arrays gathered over the shards in env order."""
         if not self._episode_stats:
             raise RuntimeError("episode statistics are off: construct the env with episode_stats=True")
-        if self.output == "torch":
-            per_dev = [{k: self._torch.as_tensor(eng.device_array(n), device=f"cuda:{dev}") for k, n in self.EPISODE_STATS.items()}
-                       for eng, dev in zip(self.engines, self.devices)]
-            return per_dev[0] if len(per_dev) == 1 else tuple(per_dev)
-        return {k: self._gather(n) for k, n in self.EPISODE_STATS.items()}
+        return self._named_buffers(self.EPISODE_STATS)
 
     def action_mask(self, permissive=False):
         """bool (B, N, 5) (`action_mask=True` only): [..., a] says whether Action a can change agent's (x, y, dir, carrying_shelf) in the
@@ -729,20 +732,15 @@ class WarehouseVecEnv(_VectorEnvBase):
         (a tuple per device when sharded).  The raw byte's bits are in include/rware_hip.h at RW_ACTION_MASK_ON."""
         if not self._action_mask:
             raise RuntimeError("action masks are off: construct the env with action_mask=True")
-        if self.output == "torch":
-            t = self._torch
-            per_dev = []
-            for eng, dev in zip(self.engines, self.devices):
-                raw = t.as_tensor(eng.device_array("action_mask"), device=f"cuda:{dev}")
-                if permissive:
-                    raw = raw | ((raw >> 4) & 2)
-                shifts = t.arange(5, dtype=t.uint8, device=raw.device)
-                per_dev.append(((raw.unsqueeze(-1) >> shifts) & 1).to(t.bool))
-            return per_dev[0] if len(per_dev) == 1 else tuple(per_dev)
-        raw = self._gather("action_mask")
-        if permissive:
-            raw = raw | ((raw >> 4) & 2)
-        return ((raw[..., None] >> np.arange(5, dtype=np.uint8)) & 1).astype(np.bool_)
+        t = self._torch if self.output == "torch" else None
+
+        def bits(raw):
+            if permissive:
+                raw = raw | ((raw >> 4) & 2)
+            if t is None:
+                return ((raw[..., None] >> np.arange(5, dtype=np.uint8)) & 1).astype(np.bool_)
+            return ((raw.unsqueeze(-1) >> t.arange(5, dtype=t.uint8, device=raw.device)) & 1).to(t.bool)
+        return bits(self._gather("action_mask")) if t is None else self._per_device(lambda view: bits(view("action_mask")))
 
     def device_tensor(self, name):
         """Zero-copy torch view of any engine buffer (single-device envs).  "obs_packed" (obs_format="packed") comes as int32 — the
@@ -768,8 +766,7 @@ class WarehouseVecEnv(_VectorEnvBase):
     def set_state(self, refresh_obs: bool = True, **fields):
         # `grid` first: later coordinate writes then re-mark the derived int32 view stale (layer 0 follows agent_x / agent_y)
         for k, v in sorted(fields.items(), key=lambda kv: kv[0] != "grid"):
-            if k not in STATE_FIELDS and k not in ("need_reset", "agent_msg", "stat_deliveries", "stat_failed_moves") \
-                    and k not in self.EPISODE_STATS.values():
+            if k not in _capi.WRITABLE_STATE:  # (the state and view rows of _capi.BUFFERS: outputs are not state)
                 raise KeyError(k)
             v = np.asarray(v)
             for eng, (lo, hi) in zip(self.engines, self._bounds):
