@@ -35,7 +35,10 @@ extern "C" {
  * all five empty without the flag), and rw_info.stats read as a bit set — bit 0 RW_STATS_ON, bit 1 RW_EPISODES_ON — so an engine with only
  * the old flag still reports 1; rw_info keeps its size.
  * Still 4, a compatible addition: RW_ACTION_MASK_ON in rw_stream_flags, RW_BUF_ACTION_MASK appended (RW_BUF_KIND_COUNT 28 -> 29; empty
- * without the flag), bit 2 of rw_info.stats; rw_info keeps its size, no new entry point. */
+ * without the flag), bit 2 of rw_info.stats; rw_info keeps its size, no new entry point.
+ * Still 4, a compatible addition: RW_OBS_IMAGE_U8 in rw_stream_flags — the elements of RW_BUF_OBS of an IMAGE / IMAGE_DICT engine become
+ * uint8 (same kind, same shape, a quarter of the bytes; RW_BUF_KIND_COUNT stays 29), rw_info.obs_packed reads 2 for such an engine;
+ * rw_info keeps its size, no new entry point. */
 #define RW_ABI_VERSION 4
 
 typedef struct rw_engine rw_engine;
@@ -192,7 +195,27 @@ enum rw_stream_flags {
      * Out of scope: a per-step mask tape for rw_step_many_device (a fused rollout is open-loop — its actions exist before the launch, so
      * nothing samples from those masks; the closed-loop forms, rw_step / graphs / pipelines, get a fresh mask every step) and masks in the
      * pipelined (PIPE=1) kernels. */
-    RW_ACTION_MASK_ON = 4096
+    RW_ACTION_MASK_ON = 4096,
+    /* uint8 IMAGE observations.  Every element of an IMAGE / IMAGE_DICT observation is an integer in 0 .. 4 (rware/warehouse.py:527-596:
+     * six layers are 0 / 1, AGENT_DIRECTION holds dir + 1); with RW_OBS_IMAGE_U8 the launches write it as ONE byte instead of a float:
+     *   RW_BUF_OBS  uint8 [B][N][C][2r+1][2r+1] — the same kind, the same shape, element for element (uint8) of the float the engine
+     *               writes without the flag; rw_info.obs_length stays the element count per agent, the buffer holds B * N * obs_length bytes
+     * (the default layer list at sensor_range 1: 45 bytes per agent instead of 180).  No unpacking step exists or is needed: a CNN's first
+     * layer takes obs.float().  rw_get_buffer / rw_read / rw_write of RW_BUF_OBS and the `obs` argument of rw_read_outputs move that many
+     * bytes (a float-sized rw_read fails with RW_ERR_INVALID_ARG); rw_info.obs_packed reads 2 and engine_bytes_per_env_step prices
+     * N * obs_length bytes for the observation.  RW_BUF_FEATURES (IMAGE_DICT), RW_BUF_FINAL_OBS and RW_BUF_FINAL_FEATURES (SAME_STEP
+     * autoreset) stay float32.  rw_step*, tapes, captured graphs, rw_multi, rw_reset (masked or not), rw_refresh_obs, snapshots' restore
+     * and the fused rollouts all produce uint8 rows; the `obs_tape` of rw_step_many_device receives uint8 [T][B][N][C][2r+1][2r+1] through
+     * the same pointer, at ANY byte address (a step's rows are B * N * obs_length bytes, odd for many shapes: the kernels look at the
+     * address of every chunk and store 16 bytes, 4 bytes or single bytes at a time).  IMAGE and IMAGE_DICT only: FLATTENED fails with
+     * RW_ERR_UNSUPPORTED (its compact format is RW_OBS_PACKED), and so do the two flags together; rw_unpack_obs and rw_debug_store_floor
+     * return RW_ERR_UNSUPPORTED on such an engine.  Off by default; the float32 image stays the default and the parity path.
+     * Which kernels run with it: as for RW_OBS_PACKED — the ahead-of-time exact-shape builds do not carry the uint8 rows and are never
+     * used; below 4096 envs, with RW_JIT_OFF or without hipRTC the generic kernel runs (rw_info.build_kind == 0); from 4096 envs on (or with
+     * RW_JIT_FORCE) rw_create compiles an exact-shape uint8 build through hipRTC at construction (rw_info.jit says which happened).
+     * Combines with RW_STATS_ON, RW_EPISODES_ON, RW_ACTION_MASK_ON and msg_bits.  RW_PIPE_ON | RW_OBS_IMAGE_U8: the classic kernel runs
+     * and rw_jit_log() says so. */
+    RW_OBS_IMAGE_U8 = 8192
 };
 
 /* Device buffers (all env-major, C-contiguous).  Replaces the attributes callers read off the
@@ -201,7 +224,8 @@ enum rw_stream_flags {
  * env.np_random.bit_generator.state, and the step() return tuple (:944-946). */
 enum rw_buffer_kind {
     RW_BUF_OBS = 0,          /* float32 [B][N][L]  FLATTENED observation (:598-674), or, for the IMAGE
-                                                   types, [B][N][C][2r+1][2r+1] (:527-596)        */
+                                                   types, [B][N][C][2r+1][2r+1] (:527-596) — uint8 elements
+                                                   with RW_OBS_IMAGE_U8                           */
     RW_BUF_REWARDS = 1,      /* float32 [B][N]                                                    */
     RW_BUF_TERMINATED = 2,   /* uint8   [B]        `done` (:935-941)                              */
     RW_BUF_TRUNCATED = 3,    /* uint8   [B]        always 0 (:942); read-only (rw_write refuses it) */
@@ -330,6 +354,7 @@ int rw_step_tape_device_timed(rw_engine *eng, const int32_t *tape_dev, int32_t t
 /* RW_OBS_PACKED engines: the signature stays, and a non-NULL `obs_tape` receives PACKED rows — uint32 [T][B][N][PW] — through the same
  * pointer (rw_unpack_obs takes any row count, so one call unpacks a whole tape).  Any 4-byte-aligned tape works; one that starts on a
  * 16-byte boundary gets 16-byte stores.
+ * RW_OBS_IMAGE_U8 engines: likewise, `obs_tape` receives uint8 [T][B][N][C][2r+1][2r+1]; a tape at any byte address works.
  * T consecutive steps from a device-resident action tape int32 [T][B][N] in ONE kernel launch: each
  * workgroup keeps its env chunk in LDS across the T steps, so per step only the actions are read and
  * obs / rewards / terminated written (rollout API; open-loop by construction —
@@ -370,7 +395,7 @@ int rw_set_stream(rw_engine *eng, void *stream);
  * the derived views on every request; this call is for graphs captured by other means. */
 int rw_mark_views_stale(rw_engine *eng);
 
-/* recompute RW_BUF_OBS (RW_OBS_PACKED: RW_BUF_OBS_PACKED) from the current state (after rw_write of state buffers) */
+/* recompute RW_BUF_OBS (RW_OBS_PACKED: RW_BUF_OBS_PACKED; RW_OBS_IMAGE_U8: as uint8) from the current state (after rw_write of state buffers) */
 int rw_refresh_obs(rw_engine *eng);
 /* packed rows -> float32 rows on the device (no reference counterpart): `packed_dev` uint32 [n_rows][PW], `obs_f32_dev` float32
  * [n_rows][L], both device pointers, one row per (env, agent) — RW_BUF_OBS_PACKED itself (n_rows = B * N), a slice of it, or a
@@ -388,7 +413,8 @@ int rw_get_buffer(rw_engine *eng, int kind, void **dev_ptr, size_t *bytes);
 /* synchronous copies between a buffer and host memory (state inspection / injection) */
 int rw_read(rw_engine *eng, int kind, void *host_dst, size_t bytes);
 /* the step() return tuple (:944-946) to host memory in one round trip: RW_BUF_OBS / REWARDS / TERMINATED (/ FEATURES) copied
- * back to back, one synchronisation; any pointer may be NULL (skipped).  `truncated` is always False (:942): nothing to read. */
+ * back to back, one synchronisation; any pointer may be NULL (skipped).  `truncated` is always False (:942): nothing to read.
+ * (RW_OBS_IMAGE_U8: `obs` receives the buffer's B * N * obs_length BYTES through the same pointer.) */
 int rw_read_outputs(rw_engine *eng, float *obs, float *rewards, uint8_t *terminated, float *features);
 int rw_write(rw_engine *eng, int kind, const void *host_src, size_t bytes);
 /* rebuild RW_BUF_GRID exactly like Warehouse._recalc_grid (:749-755) from explicit shelf
@@ -450,15 +476,16 @@ typedef struct rw_info {
     int32_t stats;                   /* a bit set: bit 0 RW_STATS_ON — RW_BUF_STAT_* are kept; bit 1 RW_EPISODES_ON — RW_BUF_EP_* are kept; bit 2 RW_ACTION_MASK_ON — RW_BUF_ACTION_MASK is written
                                         (an engine with only RW_STATS_ON reads 1, as before; was `reserved[1]`: same struct size)      */
     int32_t obs_packed;              /* 1: RW_OBS_PACKED — the launches write RW_BUF_OBS_PACKED, RW_BUF_OBS is empty; engine_bytes_per_env_step
-                                        prices the packed row (appended with ABI 4)                                                  */
+                                        prices the packed row (appended with ABI 4).  2: RW_OBS_IMAGE_U8 — the elements of RW_BUF_OBS are
+                                        uint8; engine_bytes_per_env_step prices obs_length bytes per agent                           */
 } rw_info;
 int rw_get_info(const rw_engine *eng, rw_info *out);
 /* what the run-time specialisation did for this engine: cache file / compile time, or why it is not in use ("" if not tried) */
 const char *rw_jit_log(const rw_engine *eng);
 /* the compile half of the run-time specialisation, without a device (build checks, cache warm-up on a login node): `shape` =
  * {sensor_range, H, W, N, Q, S, envs per workgroup, 256, msg_bits, wide shelf ids, observation kind (0 FLATTENED, 1 IMAGE,
- * 2 FLATTENED + messages), baked image layers, packed layer list, image_directional (-1 for FLATTENED), non-temporal stores,
- * packed observation rows (1: the build of an RW_OBS_PACKED engine)};
+ * 2 FLATTENED + messages, 3 IMAGE + messages), baked image layers, packed layer list, image_directional (-1 for FLATTENED), non-temporal stores,
+ * packed observation rows (1: the build of an RW_OBS_PACKED engine — with an IMAGE kind: of an RW_OBS_IMAGE_U8 engine)};
  * returns the size of the gfx code object (compiled or found in the disk cache), -1 on failure (`log` says why). */
 int64_t rw_jit_probe(const int32_t shape[16], const char *arch, char *log, size_t log_len);
 
@@ -481,7 +508,8 @@ int rw_event_elapsed_ms(rw_engine *eng, int32_t slot_begin, int32_t slot_end, fl
 /* measurement aid (no reference counterpart): `n_launches` back-to-back launches of a kernel that only WRITES one step's
  * observations — the engine's launch geometry and store instruction, nothing else — timed with HIP events on the first / last launch:
  * the least any kernel producing this step's observations can take on this device (bench.py reports it beside the 8 TB/s roofline).
- * RW_BUF_OBS is refreshed afterwards (rw_refresh_obs).  Uses the engine's timing-event slots 6 and 7 (rw_event_record). */
+ * RW_BUF_OBS is refreshed afterwards (rw_refresh_obs).  Uses the engine's timing-event slots 6 and 7 (rw_event_record).
+ * RW_ERR_UNSUPPORTED on an RW_OBS_IMAGE_U8 engine (the store-only kernel writes dword rows). */
 int rw_debug_store_floor(rw_engine *eng, int32_t n_launches, float *ms_per_launch);
 
 /* profiling aid: runs ONE step (device actions) with per-workgroup phase stamps taken from the

@@ -21,7 +21,7 @@ RW_OK, RW_ERR_INVALID_ARG, RW_ERR_INVALID_ACTION, RW_ERR_HIP, RW_ERR_UNSUPPORTED
 # them), "io" the launches' inputs and outputs.  Where a kind exists only with a flag (empty otherwise) the comment names it.
 _b, _bn, _bn6, _obs = (lambda e: (e.B,)), (lambda e: (e.B, e.N)), (lambda e: (e.B, e.N, 6)), (lambda e: e.obs_shape)
 BUFFERS = {
-    "obs": (0, np.float32, _obs, "io"),  # not with RW_OBS_PACKED
+    "obs": (0, np.float32, _obs, "io"),  # not with RW_OBS_PACKED; RW_OBS_IMAGE_U8: uint8 elements (Engine.dtypes overrides this row's dtype)
     "rewards": (1, np.float32, _bn, "io"),
     "terminated": (2, np.uint8, _b, "io"),
     "truncated": (3, np.uint8, _b, "io"),  # read-only
@@ -55,6 +55,7 @@ RW_PRIO_OFF, RW_PRIO_ON = 256, 512  # rw_stream_flags: raised wavefront priority
 RW_OBS_PACKED = 1024  # rw_stream_flags: bit-packed FLATTENED observations — uint32 (B, N, PW) in "obs_packed", no float32 "obs" buffer
 RW_EPISODES_ON = 2048  # rw_stream_flags: keep per-episode return / length on the device, RW_BUF_EP_RETURN .. _EP_COUNT (off by default)
 RW_ACTION_MASK_ON = 4096  # rw_stream_flags: the step kernels write a valid-action byte per agent to RW_BUF_ACTION_MASK (off by default)
+RW_OBS_IMAGE_U8 = 8192  # rw_stream_flags: IMAGE / IMAGE_DICT observations as uint8 — "obs" keeps its shape, one byte per element
 RW_STATS_ON = 128  # rw_stream_flags: keep the per-env event counters RW_BUF_STAT_DELIVERIES / _FAILED_MOVES (off by default)
 
 AUTORESET = {"disabled": 0, None: 0, "next_step": 1, "same_step": 2}
@@ -212,7 +213,7 @@ class Engine:
                  max_inactivity_steps, max_steps, reward_type, normalised_coordinates=False,
                  autoreset_mode="next_step", device_id=0, envs_per_workgroup=0,
                  threads_per_workgroup=0, stream=None, library=None, observation_type=1,
-                 image_layers=(), image_directional=True, msg_bits=0, use_given_stream=False, obs_stores=None, jit=None, pipe=None, stats=False, wave_priority=None, obs_packed=False, episodes=False, action_mask=False):
+                 image_layers=(), image_directional=True, msg_bits=0, use_given_stream=False, obs_stores=None, jit=None, pipe=None, stats=False, wave_priority=None, obs_packed=False, episodes=False, action_mask=False, obs_image_u8=False):
         self.lib = load(library)
         self._h = C.c_void_p()
         self._arena, self.arena_allocations = {}, 0  # rollout_host's device tapes (grow-only; freed in close())
@@ -229,7 +230,7 @@ class Engine:
             | {None: 0, "auto": 0, False: RW_JIT_OFF, "off": RW_JIT_OFF, True: RW_JIT_FORCE, "force": RW_JIT_FORCE}[jit]
             | {None: 0, "auto": 0, False: RW_PIPE_OFF, "off": RW_PIPE_OFF, True: RW_PIPE_ON, "on": RW_PIPE_ON}[pipe]
             | (RW_STATS_ON if stats else 0) | (RW_OBS_PACKED if obs_packed else 0) | (RW_EPISODES_ON if episodes else 0)
-            | (RW_ACTION_MASK_ON if action_mask else 0)
+            | (RW_ACTION_MASK_ON if action_mask else 0) | (RW_OBS_IMAGE_U8 if obs_image_u8 else 0)
             | {None: 0, "auto": 0, False: RW_PRIO_OFF, "off": RW_PRIO_OFF, True: RW_PRIO_ON, "on": RW_PRIO_ON}[wave_priority],
             hw.ctypes.data, goals.ctypes.data, C.c_void_p(stream or 0))
         rc = self.lib.rw_create(C.byref(cfg), C.byref(self._h))
@@ -249,7 +250,10 @@ class Engine:
         self.episodes = bool(i.stats & 2)
         self.action_mask = bool(i.stats & 4)  # bit 2 RW_ACTION_MASK_ON
         # obs_packed=True (RW_OBS_PACKED): the launches write uint32 rows of PW words to "obs_packed"; "obs" does not exist
-        self.packed = bool(i.obs_packed)
+        self.packed = i.obs_packed == 1
+        # obs_image_u8=True (RW_OBS_IMAGE_U8, rw_info.obs_packed == 2): "obs" holds uint8 elements — this engine's dtype of that row
+        self.image_u8 = i.obs_packed == 2
+        self.dtypes = dict(BUF_DTYPE, obs=np.uint8) if self.image_u8 else BUF_DTYPE
         self.obs_name = "obs_packed" if self.packed else "obs"  # the observation buffer the launches write
 
     def _check(self, rc):
@@ -308,7 +312,7 @@ class Engine:
         (obs (T,B,N,L) or None, rewards (T,B,N), terminated (T,B))."""
         a = np.ascontiguousarray(actions, dtype=np.int32).reshape(-1, self.B, self.N * (1 + self.M))
         T = a.shape[0]
-        obs = np.empty((T,) + self.shapes[self.obs_name], BUF_DTYPE[self.obs_name]) if want_obs else None  # (packed: uint32 (T,B,N,PW))
+        obs = np.empty((T,) + self.shapes[self.obs_name], self.dtypes[self.obs_name]) if want_obs else None  # (packed: uint32 (T,B,N,PW))
         rew = np.empty((T, self.B, self.N), np.float32)
         term = np.empty((T, self.B), np.uint8)
         # device tapes from the engine's arena: grow-only buffers kept for the engine's lifetime, so a training loop that
@@ -380,13 +384,13 @@ class Engine:
 
     # buffers ------------------------------------------------------------------------------
     def read(self, name) -> np.ndarray:
-        out = np.empty(self.shapes[name], dtype=BUF_DTYPE[name])
+        out = np.empty(self.shapes[name], dtype=self.dtypes[name])
         self._check(self.lib.rw_read(self._h, BUF[name], out.ctypes.data, out.nbytes))
         return out
 
     def read_outputs(self, want_features=False):
         """obs, rewards, terminated (uint8), features-or-None as fresh host arrays: one C call, one synchronisation."""
-        obs = None if self.packed else np.empty(self.shapes["obs"], np.float32)
+        obs = None if self.packed else np.empty(self.shapes["obs"], self.dtypes["obs"])
         rew = np.empty(self.shapes["rewards"], np.float32)
         term = np.empty(self.shapes["terminated"], np.uint8)
         feat = np.empty(self.shapes["features"], np.float32) if want_features else None
@@ -397,7 +401,7 @@ class Engine:
         return obs, rew, term, feat
 
     def write(self, name, array):
-        a = np.ascontiguousarray(array, dtype=BUF_DTYPE[name]).reshape(self.shapes[name])
+        a = np.ascontiguousarray(array, dtype=self.dtypes[name]).reshape(self.shapes[name])
         self._check(self.lib.rw_write(self._h, BUF[name], a.ctypes.data, a.nbytes))
 
     def unpack_obs_device(self, packed_ptr, out_ptr, n_rows):
@@ -411,7 +415,7 @@ class Engine:
         if name in ("obs", "obs_packed") and not nbytes.value:
             raise RuntimeError('this engine writes packed observations (obs_format="packed"): there is no float32 "obs" buffer — use "obs_packed" and unpack_obs'
                                if name == "obs" else 'this engine writes float32 observations: "obs_packed" exists only with obs_format="packed"')
-        return DeviceArray(ptr.value or 0, self.shapes[name], dtype or BUF_DTYPE[name], self)
+        return DeviceArray(ptr.value or 0, self.shapes[name], dtype or self.dtypes[name], self)
 
     def recalc_grid(self, shelf_xy):
         s = np.ascontiguousarray(shelf_xy, dtype=np.int32).reshape(self.B, -1, 2)
@@ -491,7 +495,7 @@ def jit_probe(*, sensor_range, H, W, N, Q, S, E, msg_bits=0, obs=0, layers=(), d
     for k, l in enumerate(layers):
         layer_bits |= int(l) << (4 * k)
     shape = (C.c_int32 * 16)(sensor_range, H, W, N, Q, S, E, 256, msg_bits, 1 if S > 255 else 0, obs, len(layers), layer_bits,
-                             (1 if directional else 0) if obs == 1 else -1, nt, int(packed))
+                             (1 if directional else 0) if obs in (1, 3) else -1, nt, int(packed))
     log = C.create_string_buffer(4096)
     n = load(library).rw_jit_probe(shape, arch.encode(), log, 4096)
     return int(n), log.value.decode(errors="replace")

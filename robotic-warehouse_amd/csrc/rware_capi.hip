@@ -65,7 +65,7 @@ struct Pipe {
 };
 
 // The opt-in outputs (rw_engine::features): one bit per switch of rw_stream_flags, each described once in kFeatures below
-enum : uint32_t { F_STATS = 1, F_EPISODES = 2, F_MASK = 4, F_PACKED = 8 };  // (all but F_PACKED: the bits of rw_info::stats)
+enum : uint32_t { F_STATS = 1, F_EPISODES = 2, F_MASK = 4, F_PACKED = 8, F_IMAGE_U8 = 16 };  // (the first three: the bits of rw_info::stats)
 
 // What a buffer kind is (kKinds below): a derived view — one of a group that refresh() unpacks from what the step kernels keep and pack()
 // packs back after a host write; the groups in the order rw_refresh_grid rebuilds them —, simulation state (part of a snapshot), or an input / output
@@ -110,7 +110,8 @@ struct rw_engine {
     uint32_t features = 0;     // F_*: the opt-in outputs this engine was asked for; their buffers are allocated (kKinds) ...
     int op_flags = 0;          // ... and every launch carries their OP_FLAG_* bits
     int PW = 0;                // words of a packed row, 1 + ceil(L / 32) (FLATTENED; 0 for the IMAGE types)
-    int row_words = 0;         // dwords per agent of the observation the launches write: L floats, or PW words when packed
+    int row_bytes = 0;         // bytes per agent of the observation the launches write: 4 L (floats), 4 PW when packed, L for uint8 images
+    int row_elems = 0;         // ... and its elements — floats, packed words, bytes: the unit of LaunchArgs::obs_stride
     int msg_bits = 0;          // communication bits per agent (FLATTENED only)
     int32_t *d_status = nullptr;
     hipEvent_t events[8]{};
@@ -330,9 +331,13 @@ int pack(rw_engine *eng, int group) {
 struct Shape {
     int B, H, W, N, Q, S, R, HW, SW;
     int L;       // floats per agent in RW_BUF_OBS
-    uint32_t features;  // F_*: the opt-in outputs asked for.  F_PACKED: the launches write uint32 rows of PW words instead (RW_BUF_OBS_PACKED)
+    uint32_t features;  // F_*: the opt-in outputs asked for.  F_PACKED: the launches write uint32 rows of PW words instead (RW_BUF_OBS_PACKED);
+                        // F_IMAGE_U8: the elements of RW_BUF_OBS are bytes
     int PW;      // words of a packed row: 1 + ceil(L / 32) (FLATTENED)
-    int row_words() const { return features & F_PACKED ? PW : L; }  // dwords per agent of the observation a step writes
+    // bytes per agent of the observation a step writes (a uint8 image row is L bytes, usually no dword multiple), and its elements (floats,
+    // packed words, bytes)
+    int row_bytes() const { return features & F_PACKED ? 4 * PW : features & F_IMAGE_U8 ? L : 4 * L; }
+    int row_elems() const { return features & F_PACKED ? PW : L; }
     int OW;      // LDS bit-string words per agent (must equal the kernel's OW): the flattened row, or n_layers image planes
     int M, AM;   // communication bits per agent (FLATTENED only); action words per agent
     int n_layers, layers[8];
@@ -351,11 +356,13 @@ struct Shape {
 
 // One row per switch.  `stats_build`: its kernel code is compiled in by RW_STATS_BUILD (else by RW_PACKED_BUILD).  `pipe`: the chunk-pipelined
 // build carries it.  `agent_bytes`, `env_bytes`: what it adds to rw_info::engine_bytes_per_env_step per agent and per env (the episode statistics:
-// the running return and length, read + write; the masks: one byte per agent, written; the packed rows are priced through row_words).  `what`,
+// the running return and length, read + write; the masks: one byte per agent, written; the packed rows and the uint8 images are priced through row_bytes).  `what`,
 // `carried`: the words of the rw_jit_log notes.  The rows stand in the order in which a message that can name only one feature picks it.
 struct Feature { uint32_t bit; int stream_flag, op_flag; bool stats_build, pipe; int agent_bytes, env_bytes; const char *flag, *what, *carried; };
 constexpr Feature kFeatures[] = {
     {F_PACKED, RW_OBS_PACKED, rw::OP_FLAG_PACKED, false, false, 0, 0, "RW_OBS_PACKED", "packed observations", "the packed rows"},
+    // (an IMAGE kernel reads the same op flag as "uint8 elements": the two formats never meet in one engine, check_config)
+    {F_IMAGE_U8, RW_OBS_IMAGE_U8, rw::OP_FLAG_PACKED, false, false, 0, 0, "RW_OBS_IMAGE_U8", "uint8 images", "the uint8 rows"},
     {F_STATS, RW_STATS_ON, rw::OP_FLAG_STATS, true, true, 0, 0, "RW_STATS_ON", "event counters", "the counting code"},
     {F_EPISODES, RW_EPISODES_ON, rw::OP_FLAG_EPISODES, true, false, 8, 8, "RW_EPISODES_ON", "episode statistics", "the code (RW_STATS_BUILD)"},
     {F_MASK, RW_ACTION_MASK_ON, rw::OP_FLAG_MASK, true, false, 1, 0, "RW_ACTION_MASK_ON", "action masks", "the code (RW_STATS_BUILD)"},
@@ -384,7 +391,9 @@ enum : uint8_t { W_ALWAYS = 0, W_FLOAT_ROWS = 16, W_FINAL, W_FINAL_DICT };
 struct Kind { int kind; const char *name; uint8_t elem; Extent ext; uint8_t with; Role role; const char *read_only = nullptr; };
 #define K(kind, ...) {RW_BUF_##kind, "RW_BUF_" #kind, __VA_ARGS__}
 constexpr Kind kKinds[] = {
-    K(OBS, 4, X_NL, W_FLOAT_ROWS, IO),  // (RW_OBS_PACKED: the float rows are neither streamed nor held — 298 MB at 262144 small-4ag envs)
+    // (RW_OBS_PACKED: the float rows are neither streamed nor held — 298 MB at 262144 small-4ag envs; RW_OBS_IMAGE_U8: the same elements,
+    //  1 byte each — kind_elem)
+    K(OBS, 4, X_NL, W_FLOAT_ROWS, IO),
     K(REWARDS, 4, X_N, W_ALWAYS, IO),
     K(TERMINATED, 1, X_1, W_ALWAYS, IO),
     // an engine-owned flag: the step kernel stores it only when it changes (truncated never does, :942), so a host write would stick
@@ -420,6 +429,9 @@ constexpr Kind kKinds[] = {
 static_assert(sizeof kKinds / sizeof kKinds[0] == RW_BUF_KIND_COUNT, "one row per RW_BUF_* kind");
 static_assert([] { int ok = 1; for (const Kind &k : kKinds) ok &= k.kind == &k - kKinds; return ok; }(), "kKinds is indexed by kind");
 
+// element size of buffer `k` with these features: the table's, except the observation of a uint8-image engine
+size_t kind_elem(const Kind &k, uint32_t features) { return k.kind == RW_BUF_OBS && (features & F_IMAGE_U8) ? 1 : k.elem; }
+
 // bytes of buffer `k` in an engine of this shape (0: the kind does not exist with this configuration)
 size_t kind_bytes(const Kind &k, const Shape &s, const rw_config *cfg) {
     const bool final_obs = cfg->autoreset_mode == RW_AUTORESET_SAME_STEP;
@@ -427,7 +439,7 @@ size_t kind_bytes(const Kind &k, const Shape &s, const rw_config *cfg) {
                         : k.with == W_FINAL_DICT ? final_obs && s.obs == RW_OBS_IMAGE_DICT : (s.features & k.with) != 0);
     const size_t N = (size_t)s.N;
     const size_t per_env[] = {1, N, N * s.L, N * s.PW, 2 * (size_t)s.HW, (size_t)s.Q, 6, N * s.AM, 6 * N};  // (by Extent)
-    return exists ? (size_t)s.B * per_env[k.ext] * k.elem : 0;
+    return exists ? (size_t)s.B * per_env[k.ext] * kind_elem(k, s.features) : 0;
 }
 
 // host checks of the config, in the order the caller sees their errors; no HIP call
@@ -490,6 +502,12 @@ int check_config(const rw_config *cfg, Shape *out) {
                     "the IMAGE types are not packed (AGENT_DIRECTION holds dir + 1)");
     if (packed && (W > 65535 || H > 65535))  // (H*W <= 10000 excludes it already: the format's own limit, kept explicit)
         return fail(nullptr, RW_ERR_UNSUPPORTED, "RW_OBS_PACKED: a packed row holds x | y << 16: grids up to 65535 cells a side");
+    if (s.features & F_IMAGE_U8) {
+        if (!s.image)  // (the FLATTENED row holds coordinates, fractions with normalised_coordinates: its compact format is RW_OBS_PACKED)
+            return fail(nullptr, RW_ERR_UNSUPPORTED, "RW_OBS_IMAGE_U8: uint8 elements exist for the IMAGE and IMAGE_DICT observation types only "
+                        "(every image element is an integer in 0..4); FLATTENED rows have RW_OBS_PACKED");
+        if (packed) return fail(nullptr, RW_ERR_UNSUPPORTED, "RW_OBS_IMAGE_U8 and RW_OBS_PACKED are two formats of the observation: pick one");
+    }
     *out = s;
     return RW_OK;
 }
@@ -516,7 +534,8 @@ int init_engine(rw_engine *eng, const rw_config *cfg, const Shape &s) {
     eng->features = s.features;
     for (const Feature &f : kFeatures) eng->op_flags |= eng->features & f.bit ? f.op_flag : 0;
     eng->PW = s.PW;
-    eng->row_words = s.row_words();
+    eng->row_bytes = s.row_bytes();
+    eng->row_elems = s.row_elems();
     RW_HIP_CREATE(hipSetDevice(cfg->device_id));
     RW_HIP_CREATE(hipGetDeviceProperties(&eng->prop, cfg->device_id));
     if (cfg->stream || (cfg->stream_flags & RW_STREAM_USE_GIVEN)) {
@@ -575,14 +594,15 @@ bool serves(const StaticEntry &se, const Shape &s) {
 // that size (large-16ag r=2 B = 16384 37.3 -> 43.7; small-19ag 28.9 vs 27.6 cached; large-16ag r=1: even).
 // (by chunk size in floats: 4544 small-4ag, 6816 small-12ag at 8 envs: the hint wins; 9088 large-16ag: even; 10792 small-19ag,
 //  23424 large-16ag r=2: it loses below the cache size; 9656 small-17ag: 26.1 vs 25.5 cached)
-// RW_OBS_PACKED: the rule is fed the packed chunk and step sizes (dwords) — the thresholds are INHERITED from the float rows, not
+// RW_OBS_PACKED: the rule is fed the packed chunk and step sizes — the thresholds are INHERITED from the float rows, not
 // re-measured: with rows 18 x smaller every registered task lands on "small chunk", i.e. on the hint.
+// RW_OBS_IMAGE_U8: likewise inherited, on the row's own byte size (a quarter of the float image's; no rounding to dwords).
 bool nt_rule(const rw_config *cfg, const Shape &s, int E) {
-    const long long chunk = (long long)E * s.N * s.row_words();  // floats (packed: words) of one workgroup's observations
-    const double obs_mb = (double)s.B * s.N * s.row_words() * 4 / 1e6;
+    const long long chunk_bytes = (long long)E * s.N * s.row_bytes();  // one workgroup's observations
+    const double obs_mb = (double)s.B * s.N * s.row_bytes() / 1e6;
     // (A/B hook RWARE_OBS_STORES: moves the default only — an explicit flag of the caller wins)
     const int mode = tri_state(cfg, "RWARE_OBS_STORES", "cached", "stream", RW_OBS_STORES_CACHED, RW_OBS_STORES_STREAM);
-    return mode ? mode > 0 : chunk <= 9500 || obs_mb > 240.0;
+    return mode ? mode > 0 : chunk_bytes <= 4 * 9500 || obs_mb > 240.0;  // (the chunk limit was measured in floats: 9500 of them)
 }
 
 // The kernel build rw_create settles on (pick_build, then try_jit_build) and the workgroup geometry that comes with it
@@ -721,7 +741,9 @@ int pick_build(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *b) {
 void try_jit_build(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *b) {
     const int mode = tri_state(cfg, "RWARE_JIT", "0", "force", RW_JIT_OFF, RW_JIT_FORCE, "off");  // 0 auto, -1 off, 1 force
     const bool aot_exact = b->kind != 0 && b->kind != 3;
-    const bool combo_ok = !(s.image && s.M > 0);
+    // (image + messages together: no float32 engine has had a specialised build, ahead of time or at run time; the uint8 images get theirs —
+    //  every image shape of an RW_OBS_IMAGE_U8 engine has a run-time build, kObs == OBS_IMAGE_MSG with the message bits baked in)
+    const bool combo_ok = !(s.image && s.M > 0) || (eng->features & F_IMAGE_U8) != 0;
     if (!combo_ok || !(mode == 1 || (mode == 0 && !aot_exact && s.B >= 4096))) return;
     const bool geom_given = cfg->envs_per_workgroup != 0 || cfg->threads_per_workgroup != 0;
     const int N = s.N, B = s.B;
@@ -750,7 +772,7 @@ void try_jit_build(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *
     rw_jit::Shape sh{};
     sh.R = s.R; sh.H = s.H; sh.W = s.W; sh.N = N; sh.Q = s.Q; sh.S = s.S; sh.E = je; sh.T = 256; sh.M = s.M;
     sh.wide = s.wide ? 1 : 0;
-    sh.obs = s.image ? rw::OBS_IMAGE : s.M > 0 ? rw::OBS_FLATTENED_MSG : rw::OBS_FLATTENED;
+    sh.obs = s.image ? (s.M > 0 ? rw::OBS_IMAGE_MSG : rw::OBS_IMAGE) : s.M > 0 ? rw::OBS_FLATTENED_MSG : rw::OBS_FLATTENED;
     sh.NL = s.image ? s.n_layers : 0;
     sh.directional = s.image ? (cfg->image_directional ? 1 : 0) : -1;
     sh.layers = s.image ? s.packed_layers() : 0;
@@ -837,7 +859,7 @@ int plan_launches(rw_engine *eng, const rw_config *cfg, const Shape &s, const Bu
     // The fused rollouts (every step of the launch raises the priority again): they gain at every agent count — small-4ag 3.95 ->
     // 3.72 us per step, medium-6ag-hard x 8192 4.20 -> 3.94, small-8ag 8.89 -> 8.33, medium-13ag 14.5 -> 13.85, large-16ag 21.75 -> 21.25
     // (profiles/r06_prio_rollout.txt) — so only the size limit applies to them.
-    const bool fits = (double)s.B * N * s.row_words() * 4 <= 200e6;  // (packed rows: their own size; the limit is the float rows')
+    const bool fits = (double)s.B * N * s.row_bytes() <= 200e6;  // (packed rows, uint8 images: their own size; the limit is the float rows')
     // (13 .. 16 agents — `wide4` below is only ever read for them: on their 4-env workgroups with the priority; on 8-env workgroups — the tiny warehouse has no 4-env build — with it
     //  only up to half a round of workgroups, where the stagger is a loss: 4096 envs large-16ag 9.52 us with the stagger, 9.00 without,
     //  8.80 with the priority instead; 8192: small-14ag 12.65 / 11.26 / 10.84; profiles/r06_1316_matrix.txt)
@@ -1253,7 +1275,8 @@ int rw_step_many_device(rw_engine *eng, const int32_t *actions_dev, int32_t n_st
     la.actions = actions_dev;
     la.n_steps = n_steps;
     la.act_stride = (int64_t)BN * (1 + eng->msg_bits);
-    if (obs_tape) { la.obs = obs_tape; la.obs_stride = (int64_t)(BN * eng->row_words); }  // (packed: uint32 [T][B][N][PW], in words)
+    // (packed: uint32 [T][B][N][PW], in words; uint8 images: [T][B][N][L] in bytes, the tape at any byte address)
+    if (obs_tape) { la.obs = obs_tape; la.obs_stride = (int64_t)(BN * eng->row_elems); }
     if (reward_tape) { la.rewards = reward_tape; la.rew_stride = (int64_t)BN; }
     if (terminated_tape) { la.terminated = terminated_tape; la.term_stride = (int64_t)eng->prm.B; }
     return launch(eng, la, rw::OP_STEP, /*rollout=*/true);
@@ -1290,10 +1313,12 @@ int rw_debug_store_floor(rw_engine *eng, int32_t n_launches, float *ms_per_launc
     // stream, HIP events on the first / last launch.  What any kernel that produces this step's observations pays at the least:
     // the practical floor beside the 8 TB/s one (bench.py `roofline.store_only_*`).  RW_BUF_OBS is refreshed afterwards.
     if (!eng || n_launches < 1 || !ms_per_launch) return RW_ERR_INVALID_ARG;
+    if (eng->features & F_IMAGE_U8)  // (the kernel writes whole dwords from a 16-byte boundary: a uint8 chunk is neither)
+        return fail(eng, RW_ERR_UNSUPPORTED, "rw_debug_store_floor: the store-only kernel writes dword rows; not with RW_OBS_IMAGE_U8");
     RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    const int per_wg = eng->step.E * eng->prm.N * eng->row_words;  // floats (RW_OBS_PACKED: the words of the packed rows — that engine's stream)
+    const int per_wg = eng->step.E * eng->prm.N * eng->row_elems;  // floats (RW_OBS_PACKED: the words of the packed rows — that engine's stream)
     float *obs = eng->la.obs;
-    const size_t total = (size_t)eng->prm.B * eng->prm.N * eng->row_words;  // (size_t, like the step kernel's offsets: past 2^31 floats for large batches)
+    const size_t total = (size_t)eng->prm.B * eng->prm.N * eng->row_elems;  // (size_t, like the step kernel's offsets: past 2^31 floats for large batches)
     for (int k = 0; k < n_launches; ++k) {
         hipEvent_t a = k == 0 ? eng->events[6] : nullptr, b = k == n_launches - 1 ? eng->events[7] : nullptr;
         if (eng->prm.nt_obs)
@@ -1419,7 +1444,8 @@ int rw_refresh_obs(rw_engine *eng) {
 
 int rw_unpack_obs(rw_engine *eng, const uint32_t *packed_dev, float *obs_f32_dev, int64_t n_rows) {
     if (!eng || n_rows < 0 || (n_rows && (!packed_dev || !obs_f32_dev))) return RW_ERR_INVALID_ARG;
-    if (eng->image) return fail(eng, RW_ERR_UNSUPPORTED, "rw_unpack_obs: packed rows exist for FLATTENED observations only");
+    if (eng->image)  // (RW_OBS_IMAGE_U8 included: a uint8 image needs no unpacking)
+        return fail(eng, RW_ERR_UNSUPPORTED, "rw_unpack_obs: packed rows exist for FLATTENED observations only");
     if (n_rows == 0) return RW_OK;
     RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
     const size_t n_floats = (size_t)n_rows * (size_t)eng->L, n_q = (n_floats + 3) / 4;
@@ -1603,8 +1629,8 @@ int rw_get_info(const rw_engine *eng, rw_info *out) {
     out->stagger_ticks = eng->step.stagger_ticks;
     out->pipe_envs_per_workgroup = eng->pipe.E;
     out->pipe_workgroups = eng->pipe.grid;
-    out->stats = (int32_t)(eng->features & ~F_PACKED);  // (a bit set, F_* as they stand: an engine with only RW_STATS_ON still reads 1)
-    out->obs_packed = eng->features & F_PACKED ? 1 : 0;
+    out->stats = (int32_t)(eng->features & kStatsBuild);  // (a bit set, F_* as they stand: an engine with only RW_STATS_ON still reads 1)
+    out->obs_packed = eng->features & F_PACKED ? 1 : eng->features & F_IMAGE_U8 ? 2 : 0;
     out->wave_priority = (eng->step.prio ? 1 : 0) | (eng->rollout.prio ? 2 : 0);
     out->specialised = eng->build_kind != 0 ? 1 : 0;
     out->build_kind = eng->build_kind;
@@ -1619,7 +1645,7 @@ int rw_get_info(const rw_engine *eng, rw_info *out) {
     // (read + write); IMAGE_DICT: the feature vectors.  The physical (PMC) traffic of a step is checked against this figure
     // (profiles/tools/sweep_collect.py), and bench.py's `frac_engine` is priced on it: a fraction of a bandwidth, never above 1.
     out->engine_bytes_per_env_step =
-        (int64_t)p.HW * (eng->wide ? 2 : 1) + 8LL * p.N + 4LL * p.N * (1 + eng->msg_bits) + 4LL * p.Q + 16 + 4LL * p.N * eng->row_words +
+        (int64_t)p.HW * (eng->wide ? 2 : 1) + 8LL * p.N + 4LL * p.N * (1 + eng->msg_bits) + 4LL * p.Q + 16 + (int64_t)p.N * eng->row_bytes +
         4LL * p.N + 1 + (eng->msg_bits ? 8LL * p.N : 0) + (p.features ? 24LL * p.N : 0);
     for (const Feature &f : kFeatures)  // (what the opt-in outputs add)
         if (eng->features & f.bit) out->engine_bytes_per_env_step += (int64_t)f.agent_bytes * p.N + f.env_bytes;

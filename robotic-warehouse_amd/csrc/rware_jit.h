@@ -25,6 +25,7 @@ struct Shape {
     int nt;                          // per-step kernel: 1 = non-temporal observation stores
     int stats;                       // 1: compiled with RW_STATS_BUILD — the event counters of RW_STATS_ON (rware_kernels.h)
     int packed;                      // 1: compiled with RW_PACKED_BUILD — a build for an RW_OBS_PACKED engine: packed rows only, no float expansion
+                                     //    (with an IMAGE `obs` kind: the build of an RW_OBS_IMAGE_U8 engine — uint8 rows only)
 };
 
 struct Result {

@@ -75,8 +75,9 @@
 #ifndef RW_STATS_BUILD
 #define RW_STATS_BUILD 0
 #endif
-// RW_PACKED_BUILD: the bit-packed observation rows of RW_OBS_PACKED (rware_phase_expand_packed.h) are compiled in — the generic kernels
-// (rware_generic.hip) and the run-time builds rw_create asks for when the caller wants packed rows (rware_jit.h).  0: nothing of it exists.
+// RW_PACKED_BUILD: the compact observation rows — the bit-packed FLATTENED rows of RW_OBS_PACKED (rware_phase_expand_packed.h) and the uint8
+// images of RW_OBS_IMAGE_U8 (rware_phase_expand_image_u8.h) — are compiled in: the generic kernels (rware_generic.hip) and the run-time
+// builds rw_create asks for when the caller wants such rows (rware_jit.h).  0: nothing of it exists.
 #ifndef RW_PACKED_BUILD
 #define RW_PACKED_BUILD 0
 #endif
@@ -197,7 +198,8 @@ struct LaunchArgs {
     // fused rollout (rw_step_many_device): n_steps consecutive steps in ONE launch; the env chunk stays
     // in LDS between steps, only actions are read and obs/rewards/terminated written per step.
     int32_t n_steps;
-    float *obs;                 // [B][N][L]; OP_FLAG_PACKED: uint32 [B][N][PW] through the same slot (obs_stride in words)
+    float *obs;                 // [B][N][L]; OP_FLAG_PACKED: uint32 [B][N][PW] through the same slot (obs_stride in words) — an IMAGE kernel:
+                                // uint8 [B][N][L] (obs_stride in bytes; the pointer may then sit at any byte address)
     float *rewards;             // [B][N]
     uint8_t *terminated;        // [B]
     const uint8_t *reset_mask;  // [B]                                                  (OP_RESET)
@@ -222,7 +224,8 @@ struct LaunchArgs {
 enum : int { OP_FLAG_TIMELINE = 0x100,
              OP_FLAG_STATS = 0x200,    // count deliveries / failed moves into Params::stat_* (see count_events, rware_phase_goals.h)
              OP_FLAG_PRIO = 0x400,     // raise the wavefronts' priority until the agent phases are done (see the kernel's prologue)
-             OP_FLAG_PACKED = 0x800,   // `obs` is uint32 [B][N][PW]: store the observation bit string as bits (RW_PACKED_BUILD kernels only)
+             OP_FLAG_PACKED = 0x800,   // `obs` is uint32 [B][N][PW]: store the observation bit string as bits — in an IMAGE kernel: `obs` is uint8
+                                       // [B][N][L], one byte per element (RW_PACKED_BUILD kernels only)
              OP_FLAG_EPISODES = 0x1000, // keep per-episode return / length in Params::ep_* (RW_STATS_BUILD kernels only; see ep_tick, rware_phase_goals.h)
              OP_FLAG_MASK = 0x2000 };   // write the per-agent valid-action bytes to Params::action_mask (RW_STATS_BUILD kernels only; see action_mask_store, rware_phase_goals.h)
 enum : int { TL_START = 0, TL_ZEROED, TL_DMA_ISSUED, TL_ENV_LOADED, TL_LOADED, TL_AGENTS, TL_RESET, TL_OBS_BITS,
@@ -518,16 +521,16 @@ rware_step_kernel(const Params *__restrict__ cp, RW_LAUNCH_PARAMS) {
 #else
     constexpr bool stats_on = false;
 #endif
-    // Packed observation rows (RW_OBS_PACKED): like the counters, the code exists only where RW_PACKED_BUILD is set.  A generic kernel carries
-    // both expansions and takes one by the (preloaded, workgroup-uniform) flag; a run-time build is made for ONE engine, so a packed one
-    // has the float expansion compiled out.
+    // Packed observation rows (RW_OBS_PACKED; the IMAGE kernels: uint8 images, RW_OBS_IMAGE_U8): like the counters, the code exists only where
+    // RW_PACKED_BUILD is set.  A generic kernel carries both expansions and takes one by the (preloaded, workgroup-uniform) flag; a run-time
+    // build is made for ONE engine, so a packed one has the float expansion compiled out.
 #if RW_PACKED_BUILD
 #ifdef __HIPCC_RTC__
     constexpr bool kPackedOnly = true;
 #else
     constexpr bool kPackedOnly = false;
 #endif
-    const bool packed_on = !kImage && (kPackedOnly || (la.op & OP_FLAG_PACKED) != 0);
+    const bool packed_on = kPackedOnly || (la.op & OP_FLAG_PACKED) != 0;
 #endif
     // Start stagger (launches of two or more rounds of workgroups; rw_create decides, bits 16.. of `op`): the workgroups of a launch
     // start together and stay in lock-step — all stage in, all run their agent phases, all store — so the memory system and the
@@ -802,6 +805,7 @@ rware_step_kernel(const Params *__restrict__ cp, RW_LAUNCH_PARAMS) {
 
 #if RW_PACKED_BUILD
 #include "rware_phase_expand_packed.h"
+#include "rware_phase_expand_image_u8.h"
     if (!packed_on) {
 #endif
 #include "rware_phase_expand.h"

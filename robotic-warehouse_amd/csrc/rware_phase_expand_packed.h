@@ -8,7 +8,7 @@
     //                 coordinate slots) are 0 in the bit string already, bits from L on belong to the next agent there and are masked
     // The row of agent i starts at bit i * L of the workgroup's string — any bit offset — so word w of it is a funnel shift over two
     // adjacent LDS words.  The destination is the launch's `obs` pointer, reinterpreted: uint32 [B][N][PW], strides in words.
-    if (packed_on) {
+    if (!kImage && packed_on) {  // (the IMAGE kernels: rware_phase_expand_image_u8.h)
         const int PW = 1 + OW;              // (OW == ceil(L / 32) for the FLATTENED kinds)
         const int nwd = nea * PW;           // words of this chunk
         uint32_t *pout = reinterpret_cast<uint32_t *>(obs_t) + (size_t)e0 * N * PW;

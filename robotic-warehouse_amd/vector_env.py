@@ -13,6 +13,8 @@ step()'s info carries Gymnasium's "episode" / "_episode" keys on the steps that 
 output reset() and step() add info["action_mask"].
 `obs_format="packed"` (opt-in, FLATTENED only): obs is uint32 (B, N, PW) instead — the same observation as bits, 16 bytes per agent
 at sensor_range 1 — and `env.unpack_obs(obs)` gives the float32 form back bit for bit (packing.py has the format).
+`obs_format="uint8"` (opt-in, IMAGE / IMAGE_DICT only): the image is uint8 (B, N, C, 2r+1, 2r+1) instead — the same values, 0 .. 4, one byte
+per element; `info["final_obs"]` and the IMAGE_DICT features stay float32.
 `obs[:, i, :]` is agent i's FLATTENED observation, i.e. element i of the reference's obs tuple
 (:944); `terminated` is the reference's `done` (:935-941); `truncated` is always False (:942).
 
@@ -112,8 +114,8 @@ def global_image_from_state(state, goals, image_layers, pad_to_shape=None):
 class _Space:
     """Shape/dtype descriptor used when gymnasium is not installed."""
 
-    def __init__(self, shape, dtype, n=None):
-        self.shape, self.dtype, self.n = tuple(shape), np.dtype(dtype), n
+    def __init__(self, shape, dtype, n=None, low=None, high=None):
+        self.shape, self.dtype, self.n, self.low, self.high = tuple(shape), np.dtype(dtype), n, low, high
 
     def __repr__(self):
         return f"Space(shape={self.shape}, dtype={self.dtype}, n={self.n})"
@@ -156,8 +158,8 @@ class WarehouseVecEnv(_VectorEnvBase):
                  envs_per_workgroup: int = 0, threads_per_workgroup: int = 0, library: str | None = None,
                  obs_stores: str | None = None, jit=None, pipe=None, stats: bool = False, wave_priority=None,
                  obs_format: str = "float32", episode_stats: bool = False, action_mask: bool = False):
-        if obs_format not in ("float32", "packed"):
-            raise ValueError('obs_format must be "float32" or "packed"')
+        if obs_format not in ("float32", "packed", "uint8"):
+            raise ValueError('obs_format must be "float32", "packed" or "uint8"')
         if not 0 <= int(msg_bits) <= 16:
             raise ValueError("msg_bits must be in 0..16")
         self.msg_bits = int(msg_bits)
@@ -171,6 +173,11 @@ class WarehouseVecEnv(_VectorEnvBase):
         self._packed = obs_format == "packed"
         if self._packed and self._dict_obs:
             raise ValueError('obs_format="packed" is the FLATTENED vector as bits: use observation_type=FLATTENED (dict_from_flat takes unpacked input)')
+        # "uint8": the IMAGE / IMAGE_DICT observation with one byte per element (RW_OBS_IMAGE_U8) — same shape, every value is an integer in
+        # 0 .. 4; reset() / step() / rollout() / capture_loop hand out uint8 arrays (IMAGE_DICT: the features stay float32), final_obs stays float32
+        self._image_u8 = obs_format == "uint8"
+        if self._image_u8 and self.observation_type not in (ObservationType.IMAGE, ObservationType.IMAGE_DICT):
+            raise ValueError('obs_format="uint8" exists for observation_type IMAGE and IMAGE_DICT only (FLATTENED has obs_format="packed")')
         engine_obs_type = ObservationType.FLATTENED if self._dict_obs else self.observation_type
         layers = tuple(ImageLayer(enum_value(l)) for l in (image_observation_layers or DEFAULT_IMAGE_LAYERS))
         # AGENT_DIRECTION / AGENT_LOAD are written with transposed indices by the reference (rware/warehouse.py:552,558):
@@ -257,6 +264,8 @@ class WarehouseVecEnv(_VectorEnvBase):
                 wave_priority=wave_priority,
                 # obs_format="packed": RW_OBS_PACKED (the engine refuses the IMAGE types with it)
                 obs_packed=self._packed,
+                # obs_format="uint8": RW_OBS_IMAGE_U8
+                obs_image_u8=self._image_u8,
                 # True: the engine keeps per-episode return / length on the device (RW_EPISODES_ON) — see episode_stats()
                 episodes=episode_stats,
                 # True: the step kernels write the valid-action byte of every agent (RW_ACTION_MASK_ON) — see action_mask()
@@ -284,10 +293,23 @@ class WarehouseVecEnv(_VectorEnvBase):
         if self.observation_type in (ObservationType.IMAGE, ObservationType.IMAGE_DICT):
             win = 2 * self.sensor_range + 1
             shape = (len(self.image_observation_layers), win, win)
-            self.single_observation_space = tuple(_Space(shape, np.float32) for _ in range(n))
             self.single_action_space = tuple(_Space((), np.int64, n=len(Action)) for _ in range(n))
-            self.observation_space = _Space((b, n) + shape, np.float32)
             self.action_space = _Space((b, n), np.int64, n=len(Action))
+            if self._image_u8:  # every element is an integer in 0 .. 4 (AGENT_DIRECTION holds dir + 1): Box(0, 4, uint8) of the image shape
+                sp = _gym.spaces if _gym is not None else None
+
+                def box(sh, dt, lo, hi):
+                    return sp.Box(low=lo, high=hi, shape=sh, dtype=dt) if sp else _Space(sh, dt, low=lo, high=hi)
+                one, batch = box(shape, np.uint8, 0, 4), box((b, n) + shape, np.uint8, 0, 4)
+                if self.observation_type == ObservationType.IMAGE_DICT:  # the Dict of the reference (:739-742), the image entry in uint8
+                    as_dict, inf = (getattr(sp, "Dict", dict) if sp else dict), float("inf")
+                    one = as_dict({"image": one, "features": box((6,), np.float32, -inf, inf)})
+                    batch = as_dict({"image": batch, "features": box((b, n, 6), np.float32, -inf, inf)})
+                self.single_observation_space = tuple(one for _ in range(n))
+                self.observation_space = batch
+                return
+            self.single_observation_space = tuple(_Space(shape, np.float32) for _ in range(n))
+            self.observation_space = _Space((b, n) + shape, np.float32)
             return
         # the observation spaces: float32 (L,) per agent, or — obs_format="packed" — uint32 rows of PW words per agent (packing.py);
         # the action spaces are the same for both
@@ -499,7 +521,7 @@ class WarehouseVecEnv(_VectorEnvBase):
             actions = actions.to(t.int32).contiguous()
         dev = actions.device
         # (packed: the uint32 rows as an int32 tensor — same bits; torch's uint32 has no shift ops — unpack_obs takes it as is)
-        obs = t.empty((T,) + tuple(eng.shapes[eng.obs_name]), dtype=t.int32 if self._packed else t.float32, device=dev) if want_obs else None
+        obs = t.empty((T,) + tuple(eng.shapes[eng.obs_name]), dtype=t.int32 if self._packed else t.uint8 if self._image_u8 else t.float32, device=dev) if want_obs else None
         rew = t.empty((T, self.num_envs, self.n_agents), dtype=t.float32, device=dev)
         term = t.empty((T, self.num_envs), dtype=t.uint8, device=dev)
         self._live_actions = actions
@@ -744,7 +766,7 @@ class WarehouseVecEnv(_VectorEnvBase):
 
     def device_tensor(self, name):
         """Zero-copy torch view of any engine buffer (single-device envs).  "obs_packed" (obs_format="packed") comes as int32 — the
-        uint32 rows' bits; "obs" does not exist with that format and raises."""
+        uint32 rows' bits; "obs" does not exist with that format and raises.  obs_format="uint8": "obs" is a torch.uint8 tensor."""
         import torch
 
         dt = np.int32 if name == "obs_packed" else None
