@@ -38,7 +38,9 @@ extern "C" {
  * without the flag), bit 2 of rw_info.stats; rw_info keeps its size, no new entry point.
  * Still 4, a compatible addition: RW_OBS_IMAGE_U8 in rw_stream_flags — the elements of RW_BUF_OBS of an IMAGE / IMAGE_DICT engine become
  * uint8 (same kind, same shape, a quarter of the bytes; RW_BUF_KIND_COUNT stays 29), rw_info.obs_packed reads 2 for such an engine;
- * rw_info keeps its size, no new entry point. */
+ * rw_info keeps its size, no new entry point.
+ * Still 4, a compatible addition: two entry points, rw_seed_device and rw_reset_device (seeding and masked reset from DEVICE arrays,
+ * enqueue only); no struct, flag or buffer kind changes, rw_reset itself is unchanged. */
 #define RW_ABI_VERSION 4
 
 typedef struct rw_engine rw_engine;
@@ -327,6 +329,28 @@ const char *rw_last_error(const rw_engine *eng);
  *   mask:  host [B] or NULL (all).  Only envs with mask[e] != 0 are reseeded/reset.
  * Observations of all envs are refreshed in RW_BUF_OBS. */
 int rw_reset(rw_engine *eng, const uint64_t *seeds, const uint8_t *mask);
+
+/* The same two operations from DEVICE arrays (no reference counterpart for the form; the semantics are Warehouse.seed / Warehouse.reset):
+ *   seeds_dev: device uint64 [B], 8-byte aligned.  Env e gets the PCG64 state of numpy SeedSequence(seeds_dev[e]) — one kernel, one
+ *              lane per env, the hash rw_seed_state runs on the host; has_uint32 / uinteger become 0.  rw_reset_device: or NULL — the
+ *              envs' own streams continue.
+ *   mask_dev:  device uint8 [B] or NULL (all).  Only envs with mask_dev[e] != 0 are reseeded / reset; every other env keeps all six
+ *              RNG fields bit for bit (and, for the reset, its state).
+ * Asynchrony: both calls ONLY ENQUEUE on the engine's stream — no host synchronisation, no host read of either array, no allocation.
+ *   Both are therefore legal while that stream is being captured into a HIP graph, and a captured call is replayed with the graph
+ *   (it then reads the arrays' contents of the replay).  The arrays must stay valid until the work has executed.
+ * Results: behind the seed kernel rw_reset_device makes exactly the launch rw_reset makes (the same capture detection, the derived
+ *   views marked stale), so everything rw_reset produces comes out identically: RW_BUF_OBS / RW_BUF_OBS_PACKED / uint8 rows of ALL envs
+ *   refreshed, RW_BUF_ACTION_MASK, the running episode statistics of the reset envs zeroed.  rw_seed_device reseeds and nothing else
+ *   (Warehouse.seed, :962-964).
+ * Mask aliasing: mask_dev may be RW_BUF_TERMINATED itself — with autoreset disabled, "reset what just ended".  The reset launch rewrites
+ *   that buffer, so rw_reset_device always copies the mask (asynchronous, device to device, B bytes) into a buffer of the engine's
+ *   first; both kernels read the copy.
+ * Errors: RW_ERR_INVALID_ARG for a NULL engine and for a seeds_dev that is not 8-byte aligned; rw_seed_device(eng, NULL, ...) too. */
+/* Warehouse.seed (:962-964) for the envs with mask_dev[e] != 0 (all when NULL), from DEVICE arrays; enqueue only */
+int rw_seed_device(rw_engine *eng, const uint64_t *seeds_dev, const uint8_t *mask_dev);
+/* rw_reset with DEVICE arrays: uint64 [B] seeds (or NULL: the envs' own streams continue), uint8 [B] mask (or NULL: all) */
+int rw_reset_device(rw_engine *eng, const uint64_t *seeds_dev, const uint8_t *mask_dev);
 
 /* replaces Warehouse.step(actions) (:804-946) for all B envs.
  *   rw_step:        actions is a HOST array int32 [B][N] ([B][N][1+M] with msg_bits = M); copied into a

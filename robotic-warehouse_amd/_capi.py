@@ -88,6 +88,7 @@ EXPORTS = (
     "rw_recalc_grid", "rw_get_info", "rw_seed_state", "rw_event_record", "rw_event_elapsed_ms",
     "rw_abi_version", "rw_debug_timeline", "rw_debug_store_floor", "rw_device_malloc", "rw_device_free", "rw_copy_to_device",
     "rw_copy_to_host", "rw_selftest", "rw_snapshot_create", "rw_snapshot_save", "rw_snapshot_restore", "rw_snapshot_destroy",
+    "rw_seed_device", "rw_reset_device",
 )
 
 _libs = {}
@@ -132,6 +133,8 @@ def load(path: str | None = None):
     lib.rw_last_error.argtypes = [vp]
     lib.rw_last_error.restype = C.c_char_p
     lib.rw_reset.argtypes = [vp, vp, vp]
+    lib.rw_seed_device.argtypes = [vp, vp, vp]
+    lib.rw_reset_device.argtypes = [vp, vp, vp]
     lib.rw_step.argtypes = [vp, vp]
     lib.rw_step_device.argtypes = [vp, vp]
     lib.rw_step_many_device.argtypes = [vp, vp, i32, vp, vp, vp]
@@ -284,6 +287,15 @@ class Engine:
         s = None if seeds is None else np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(self.B))
         m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(np.uint8).reshape(self.B))
         self._check(self.lib.rw_reset(self._h, None if s is None else s.ctypes.data, None if m is None else m.ctypes.data))
+
+    def reset_device(self, seeds_ptr=0, mask_ptr=0):
+        """rw_reset_device: reset() from DEVICE arrays — uint64 [B] seeds (0: the envs' own streams continue), uint8 [B] mask (0: all);
+        enqueue only (no synchronisation, no host read: legal inside a stream capture).  The arrays must outlive the enqueued work."""
+        self._check(self.lib.rw_reset_device(self._h, C.c_void_p(int(seeds_ptr or 0)), C.c_void_p(int(mask_ptr or 0))))
+
+    def seed_device(self, seeds_ptr, mask_ptr=0):
+        """rw_seed_device: the envs with a non-zero mask byte (0: all) get the PCG64 state of SeedSequence(seeds[e]); enqueue only."""
+        self._check(self.lib.rw_seed_device(self._h, C.c_void_p(int(seeds_ptr or 0)), C.c_void_p(int(mask_ptr or 0))))
 
     def step_host(self, actions_i32):
         a = np.ascontiguousarray(actions_i32, dtype=np.int32)

@@ -173,6 +173,22 @@ __global__ void __launch_bounds__(256) rware_unpack_obs_kernel(const uint32_t *_
         for (int j = 0; j < n; ++j) out[f + j] = e[j];
     }
 }
+
+// rw_seed_device / rw_reset_device: SeedSequence(seeds[e]) -> PCG64 state of env e, one lane per env (rw::pcg_seed_state: some sixty
+// 32-bit multiplies and two 128-bit ones; no LDS, no atomics).  Each lane reads 8 bytes of seed and one mask byte and writes its column
+// of the field-major RNG buffer uint64 [6][B] — six stores, each coalesced across the wavefront; has_uint32 and uinteger become 0.
+// An env whose mask byte is 0 keeps all six fields untouched (`mask` NULL: every env is reseeded).
+template <typename Dummy = void>
+__global__ void __launch_bounds__(256) rware_seed_kernel(const uint64_t *__restrict__ seeds, const uint8_t *__restrict__ mask,
+                                                          uint64_t *__restrict__ rng, int B) {
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= B) return;
+    if (mask && !mask[e]) return;
+    uint64_t st[6];
+    pcg_seed_state(seeds[e], st);
+#pragma unroll
+    for (int f = 0; f < 6; ++f) rng[(size_t)f * (size_t)B + (size_t)e] = st[f];
+}
 }  // namespace rw
 
 namespace {
@@ -1087,49 +1103,9 @@ const char *rw_last_error(const rw_engine *eng) { return eng ? eng->err.c_str() 
 int rw_seed_state(uint64_t seed, uint64_t out[6]) {
     // numpy SeedSequence(entropy=seed).generate_state(4, uint64) -> PCG64(seed_seq) initial state.
     // Replaces gymnasium.utils.seeding.np_random(seed), reached from Warehouse.reset(seed=...)
-    // (rware/warehouse.py:758-760).
+    // (rware/warehouse.py:758-760).  The hash itself: rw::pcg_seed_state (rware_pcg64.h), shared with rware_seed_kernel.
     if (!out) return RW_ERR_INVALID_ARG;
-    uint32_t ent[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-    const int n_ent = ent[1] ? 2 : 1;
-    uint32_t pool[4], hc = 0x43b0d7e5u;
-    auto hashmix = [&hc](uint32_t v) {
-        v ^= hc;
-        hc *= 0x931e8875u;
-        v *= hc;
-        v ^= v >> 16;
-        return v;
-    };
-    auto mix = [](uint32_t x, uint32_t y) {
-        uint32_t r = 0xca01f9ddu * x - 0x4973f715u * y;
-        r ^= r >> 16;
-        return r;
-    };
-    for (int i = 0; i < 4; ++i) pool[i] = hashmix(i < n_ent ? ent[i] : 0u);
-    for (int s = 0; s < 4; ++s)
-        for (int d = 0; d < 4; ++d)
-            if (s != d) pool[d] = mix(pool[d], hashmix(pool[s]));
-    uint32_t w[8], hb = 0x8b51f9ddu;
-    for (int i = 0; i < 8; ++i) {
-        uint32_t v = pool[i & 3] ^ hb;
-        hb *= 0x58f38dedu;
-        v *= hb;
-        v ^= v >> 16;
-        w[i] = v;
-    }
-    uint64_t s64[4];
-    for (int i = 0; i < 4; ++i) s64[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
-    const rw::u128 initstate = (((rw::u128)s64[0]) << 64) | s64[1];
-    const rw::u128 initseq = (((rw::u128)s64[2]) << 64) | s64[3];
-    rw::u128 inc = (initseq << 1) | 1u, state = 0;
-    state = state * rw::pcg_mult() + inc;
-    state += initstate;
-    state = state * rw::pcg_mult() + inc;
-    out[0] = (uint64_t)(state >> 64);
-    out[1] = (uint64_t)state;
-    out[2] = (uint64_t)(inc >> 64);
-    out[3] = (uint64_t)inc;
-    out[4] = 0;
-    out[5] = 0;
+    rw::pcg_seed_state(seed, out);
     return RW_OK;
 }
 
@@ -1211,6 +1187,41 @@ int rw_reset(rw_engine *eng, const uint64_t *seeds, const uint8_t *mask) {
         RW_HIP(eng, hipMemsetAsync(eng->d_mask, 1, (size_t)B, eng->stream));
     }
     return launch(eng, eng->la, rw::OP_RESET);
+}
+
+namespace {
+// the seed kernel on the engine's stream: envs with mask_dev[e] != 0 (all when NULL) get the PCG64 state of SeedSequence(seeds_dev[e])
+int seed_launch(rw_engine *eng, const uint64_t *seeds_dev, const uint8_t *mask_dev) {
+    const int B = eng->prm.B;
+    hipLaunchKernelGGL((rw::rware_seed_kernel<>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, eng->stream, seeds_dev, mask_dev,
+                       at<uint64_t>(eng, RW_BUF_RNG), B);
+    RW_HIP(eng, hipGetLastError());
+    return RW_OK;
+}
+}  // namespace
+
+int rw_seed_device(rw_engine *eng, const uint64_t *seeds_dev, const uint8_t *mask_dev) {
+    if (!eng || !seeds_dev || ((uintptr_t)seeds_dev & 7u)) return RW_ERR_INVALID_ARG;
+    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
+    return seed_launch(eng, seeds_dev, mask_dev);  // (the RNG streams are state, no derived view: nothing turns stale)
+}
+
+int rw_reset_device(rw_engine *eng, const uint64_t *seeds_dev, const uint8_t *mask_dev) {
+    if (!eng || ((uintptr_t)seeds_dev & 7u)) return RW_ERR_INVALID_ARG;
+    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
+    const int B = eng->prm.B;
+    // Enqueue only: nothing here reads either array, waits or allocates, so all of it can be recorded into a HIP graph.
+    // The mask ALWAYS goes through a device-to-device copy into the engine's own mask buffer.  It may be RW_BUF_TERMINATED itself
+    // ("reset what just ended"), which the reset launch rewrites.  That the launch reads every mask byte before any workgroup
+    // rewrites it is NOT claimed: it would have to be shown for every build (generic, exact-shape, run-time) and kept true by every
+    // later kernel change.  So the copy is never skipped — B bytes on the stream, ordered in front of both kernels.
+    if (mask_dev) RW_HIP(eng, hipMemcpyAsync(eng->d_mask, mask_dev, (size_t)B, hipMemcpyDeviceToDevice, eng->stream));
+    else RW_HIP(eng, hipMemsetAsync(eng->d_mask, 1, (size_t)B, eng->stream));
+    if (seeds_dev) {
+        const int rc = seed_launch(eng, seeds_dev, eng->d_mask);
+        if (rc != RW_OK) return rc;
+    }
+    return launch(eng, eng->la, rw::OP_RESET);  // exactly rw_reset's launch (capture detection and stale views included)
 }
 
 int rw_step_device(rw_engine *eng, const int32_t *actions_dev) {

@@ -47,6 +47,60 @@ RW_HD uint32_t pcg_next32(Pcg64 &g) {
     return (uint32_t)n;
 }
 
+// numpy SeedSequence(entropy=seed).generate_state(4, uint64) -> PCG64(seed_seq) initial state, as the 6 uint64 of an RW_BUF_RNG
+// column {state hi, state lo, inc hi, inc lo, has_uint32 = 0, uinteger = 0}: what gymnasium.utils.seeding.np_random(seed) starts
+// from (rware/warehouse.py:758-760).  The entropy words are the seed's low and — only if non-zero — high 32 bits; the pool has 4 words.
+// Host (rw_seed_state, rw_reset) and device (rware_seed_kernel) run this one function.
+RW_HD void pcg_seed_state(uint64_t seed, uint64_t out[6]) {
+    const uint32_t ent[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    const int n_ent = ent[1] ? 2 : 1;
+    uint32_t pool[4], hc = 0x43b0d7e5u;
+    auto hashmix = [&hc](uint32_t v) {
+        v ^= hc;
+        hc *= 0x931e8875u;
+        v *= hc;
+        v ^= v >> 16;
+        return v;
+    };
+    auto mix = [](uint32_t x, uint32_t y) {
+        uint32_t r = 0xca01f9ddu * x - 0x4973f715u * y;
+        r ^= r >> 16;
+        return r;
+    };
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pool[i] = hashmix(i < n_ent ? ent[i & 1] : 0u);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+            if (s != d) pool[d] = mix(pool[d], hashmix(pool[s]));
+    uint32_t w[8], hb = 0x8b51f9ddu;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        uint32_t v = pool[i & 3] ^ hb;
+        hb *= 0x58f38dedu;
+        v *= hb;
+        v ^= v >> 16;
+        w[i] = v;
+    }
+    uint64_t s64[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s64[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
+    const u128 initstate = (((u128)s64[0]) << 64) | s64[1];
+    const u128 initseq = (((u128)s64[2]) << 64) | s64[3];
+    const u128 inc = (initseq << 1) | 1u;
+    u128 state = 0;
+    state = state * pcg_mult() + inc;
+    state += initstate;
+    state = state * pcg_mult() + inc;
+    out[0] = (uint64_t)(state >> 64);
+    out[1] = (uint64_t)state;
+    out[2] = (uint64_t)(inc >> 64);
+    out[3] = (uint64_t)inc;
+    out[4] = 0;
+    out[5] = 0;
+}
+
 // uniform integer in [0, rng] (inclusive); rng == 0 consumes nothing, as in numpy
 RW_HD uint32_t pcg_bounded(Pcg64 &g, uint32_t rng) {
     if (rng == 0) return 0;

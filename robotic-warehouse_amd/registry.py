@@ -6,6 +6,7 @@ suffixes resolve here to the same constructor kwargs.
 """
 from __future__ import annotations
 
+import numbers
 import re
 
 from .enums import RewardType
@@ -129,9 +130,12 @@ class Pipeline:
         return ctx.__exit__(*exc)
 
     def reset(self, seed=None, **kw):
-        """reset of this sub-batch with the seeds its envs have in the whole batch (env i: seed + i)."""
+        """reset of this sub-batch with the seeds its envs have in the whole batch (env i: seed + i).  Device tensors (a `seed` of
+        hi - lo per-env seeds, a `mask=`) go through as they are: the sub-batch's own slice, enqueued on this pipeline's stream."""
         with self:
-            return self.env.reset(seed=None if seed is None else int(seed) + self.lo, **kw)
+            if seed is None or not isinstance(seed, numbers.Real):   # (a tensor or a per-env sequence)
+                return self.env.reset(seed=seed, **kw)
+            return self.env.reset(seed=int(seed) + self.lo, **kw)
 
 
 def make_pipelines(num_envs: int, n: int = 2, device: int = 0, env_id: str = None, **kwargs):

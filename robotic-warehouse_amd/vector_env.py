@@ -111,6 +111,13 @@ def global_image_from_state(state, goals, image_layers, pad_to_shape=None):
     return img
 
 
+def _is_tensor_arg(x):
+    """A torch tensor, or a non-empty list / tuple of them (one per shard) — told by duck typing: torch is imported only by output="torch" envs."""
+    if isinstance(x, (list, tuple)):
+        return bool(x) and all(hasattr(v, "is_cuda") and hasattr(v, "data_ptr") for v in x)
+    return hasattr(x, "is_cuda") and hasattr(x, "data_ptr")
+
+
 class _Space:
     """Shape/dtype descriptor used when gymnasium is not installed."""
 
@@ -342,7 +349,27 @@ class WarehouseVecEnv(_VectorEnvBase):
     def reset(self, *, seed=None, options=None, mask=None):
         """Warehouse.reset (:757-802) for every env (or those in `mask`).  `seed` int -> env i gets
         seed + i (Gymnasium vector convention); a sequence gives per-env seeds; None continues each
-        env's own PCG64 stream (first ever reset: a fresh OS-entropy base seed)."""
+        env's own PCG64 stream (first ever reset: a fresh OS-entropy base seed).
+        `options={"reset_mask": m}` (Gymnasium 1.x's partial reset) is `mask=m`; giving both raises ValueError, other keys are ignored.
+
+        Device path (output="torch"): when `seed` or `mask` is a CUDA tensor on the env's device the call only ENQUEUES
+        (rw_reset_device: seeding kernel + reset launch on the env's stream) — no synchronisation, no host read, so it can run behind
+        a policy and inside capture_loop.  `mask`: bool or uint8 (B,).  `seed`: int64 or uint64 (B,) — an int64 tensor is REINTERPRETED
+        as uint64 (same bits: non-negative values mean themselves, -1 means 2**64 - 1); a Python int gives env i `seed + i` (built with
+        torch.arange on the device; ValueError if seed + B exceeds 2**63); a host sequence is uploaded with a non-blocking copy, and so
+        is a host mask beside a device seed.  The tensors must be ordered on the env's stream (torch's current stream when the env was
+        built, `loop.stream` after capture_loop), like device actions.  A multi-device env takes a list with one tensor per shard, as
+        step() does.  The zero-copy observation tensors are returned, as from any reset() of a torch env."""
+        if options is not None and options.get("reset_mask") is not None:
+            if mask is not None:
+                raise ValueError('pass the partial-reset mask once: either mask= or options["reset_mask"]')
+            mask = options["reset_mask"]
+        if _is_tensor_arg(seed) or _is_tensor_arg(mask):
+            seeds_d, masks_d = self._device_seeds_masks(seed, mask, fresh_entropy=True)
+            for eng, sd, md in zip(self.engines, seeds_d, masks_d):
+                eng.reset_device(0 if sd is None else sd.data_ptr(), 0 if md is None else md.data_ptr())
+            self._live_reset = (seeds_d, masks_d)  # alive until the next reset replaces them (stream-ordered allocator: see step_async)
+            return self._observations(), {}
         seeds = None
         if seed is None and not self._seeded:
             seed = int.from_bytes(os.urandom(7), "little")
@@ -358,6 +385,57 @@ class WarehouseVecEnv(_VectorEnvBase):
         for eng, (lo, hi) in zip(self.engines, self._bounds):
             eng.reset(None if seeds is None else seeds[lo:hi], None if m is None else m[lo:hi])
         return self._observations(), ({"action_mask": self.action_mask()} if self._action_mask and self.output != "torch" else {})
+
+    def _device_seeds_masks(self, seed, mask, fresh_entropy):
+        """The device path's arguments, checked: (seeds, masks), each a list with one contiguous CUDA tensor (or None) per shard — seeds as
+        int64 / uint64 (B_shard,), masks as uint8 (a bool tensor reinterpreted, not cast).  Nothing here waits for the device."""
+        t = self._torch
+        if t is None:
+            raise ValueError('device seeds / masks need output="torch": only such an env enqueues on the stream the tensors are ordered on')
+        if seed is None and fresh_entropy and not self._seeded:
+            seed = int.from_bytes(os.urandom(7), "little")
+        n = len(self.engines)
+
+        def shards(x, what, dtypes, host_dtype):
+            if x is None:
+                return [None] * n
+            if isinstance(x, (list, tuple)) and x and all(isinstance(v, t.Tensor) for v in x):
+                if len(x) != n:
+                    raise ValueError(f"expected {n} per-device {what} tensors, got {len(x)}")
+                parts = list(x)
+            elif isinstance(x, t.Tensor):
+                if n != 1:
+                    raise ValueError(f"a multi-device env takes one {what} tensor per device (a list), or a host array")
+                parts = [x]
+            else:  # a host sequence beside a device argument: uploaded, one non-blocking copy per shard
+                h = np.ascontiguousarray(np.asarray(x).astype(host_dtype).reshape(self.num_envs))
+                h = h.view(np.int64) if host_dtype is np.uint64 else h
+                parts = [t.from_numpy(h[lo:hi]).to(f"cuda:{dev}", non_blocking=True) for dev, (lo, hi) in zip(self.devices, self._bounds)]
+            out = []
+            for d, (v, (lo, hi)) in enumerate(zip(parts, self._bounds)):
+                if not v.is_cuda or v.device.index != self.devices[d]:
+                    raise ValueError(f"the {what} tensor of shard {d} must live on cuda:{self.devices[d]}")
+                if tuple(v.shape) != (hi - lo,):
+                    raise ValueError(f"the {what} tensor of shard {d} must have shape ({hi - lo},), got {tuple(v.shape)}")
+                if v.dtype not in dtypes:
+                    raise ValueError(f"the {what} tensor must be one of {dtypes}, got {v.dtype}")
+                v = v.contiguous()
+                out.append(v.view(t.uint8) if v.dtype == t.bool else v)
+            return out
+
+        masks = shards(mask, "mask", (t.bool, t.uint8), np.uint8)
+        if seed is not None and np.isscalar(seed):
+            if int(seed) < 0:
+                raise ValueError(f"Seed must be a non-negative integer, got {seed!r}")
+            if int(seed) + self.num_envs > 2 ** 63:
+                raise ValueError(f"seed + num_envs must not exceed 2**63 on the device path (int64 arange), got seed {seed!r}")
+            # (arange(hi - lo) + base: the largest value is seed + hi - 1 <= 2**63 - 1, where arange(base, base + n) could not name its end)
+            seeds = [t.arange(hi - lo, dtype=t.int64, device=f"cuda:{dev}") + (int(seed) + lo) for dev, (lo, hi) in zip(self.devices, self._bounds)]
+        else:
+            seeds = shards(seed, "seed", (t.int64, t.uint64), np.uint64)
+        if seed is not None:
+            self._seeded = True
+        return seeds, masks
 
     def step(self, actions):
         """Warehouse.step (:804-946) for every env; actions (B, N) ints in 0..4 or Action members.
@@ -541,6 +619,9 @@ class WarehouseVecEnv(_VectorEnvBase):
         eager env.step() calls keep working (they enqueue on the env's new stream: order them with `loop.stream` yourself).
         `policy` is called `warmup` times eagerly first (outputs discarded, the env does not step) so that lazy library
         initialisation happens outside the capture.
+        `policy` may also reset: `envs.reset(seed=seed_tensor, mask=terminated)` with device tensors in front of computing its actions is
+        enqueue-only (rw_reset_device) and is captured with the rest — with autoreset_mode="disabled", "restart what just ended, with
+        these seeds" inside the graph; a seed tensor updated in place (`counter += 1`) gives every replay its own seeds.
         Returns an object with `.replay()` (enqueue the captured rounds once more), `.graph` and `.stream`."""
         t = self._torch
         if t is None or len(self.engines) != 1:
@@ -826,10 +907,20 @@ class WarehouseVecEnv(_VectorEnvBase):
         return self._observations()
 
     # ------------------------------------------------------------------------------- the rest of Warehouse's public surface
-    def seed(self, seed=None):
+    def seed(self, seed=None, mask=None):
         """Warehouse.seed (rware/warehouse.py:962-964): re-seed the RNG streams without resetting — env i gets
-        `np_random(seed + i)` (the vector convention of reset(seed=...)); None leaves them alone."""
+        `np_random(seed + i)` (the vector convention of reset(seed=...)); None leaves them alone.
+        Device path (output="torch"): a CUDA tensor for `seed` (int64 / uint64 (B,), as for reset()), or a Python int together with a
+        CUDA `mask` (bool / uint8 (B,): only those envs are reseeded), is enqueued on the env's stream (rw_seed_device) — nothing waits."""
         if seed is None:
+            return
+        if _is_tensor_arg(seed) or mask is not None:
+            if not (_is_tensor_arg(seed) or _is_tensor_arg(mask)):
+                raise ValueError("seed(seed, mask=...) is the device path: `mask` must be a CUDA tensor (reset(seed=, mask=) takes host masks)")
+            seeds_d, masks_d = self._device_seeds_masks(seed, mask, fresh_entropy=False)
+            for eng, sd, md in zip(self.engines, seeds_d, masks_d):
+                eng.seed_device(sd.data_ptr(), 0 if md is None else md.data_ptr())
+            self._live_seed = (seeds_d, masks_d)
             return
         if int(seed) < 0:
             raise ValueError(f"Seed must be a non-negative integer, got {seed!r}")
