@@ -40,7 +40,9 @@ extern "C" {
  * uint8 (same kind, same shape, a quarter of the bytes; RW_BUF_KIND_COUNT stays 29), rw_info.obs_packed reads 2 for such an engine;
  * rw_info keeps its size, no new entry point.
  * Still 4, a compatible addition: two entry points, rw_seed_device and rw_reset_device (seeding and masked reset from DEVICE arrays,
- * enqueue only); no struct, flag or buffer kind changes, rw_reset itself is unchanged. */
+ * enqueue only); no struct, flag or buffer kind changes, rw_reset itself is unchanged.
+ * Still 4, a compatible addition: one entry point, rw_global_image (Warehouse.get_global_image built on the device into an array of the
+ * caller's, enqueue only); no struct, flag or buffer kind changes (RW_BUF_KIND_COUNT stays 29). */
 #define RW_ABI_VERSION 4
 
 typedef struct rw_engine rw_engine;
@@ -427,6 +429,29 @@ int rw_refresh_obs(rw_engine *eng);
  * normalised_coordinates) are the engine's.  The result equals what RW_BUF_OBS would hold, bit for bit.  Any FLATTENED engine, with or
  * without RW_OBS_PACKED. */
 int rw_unpack_obs(rw_engine *eng, const uint32_t *packed_dev, float *obs_f32_dev, int64_t n_rows);
+
+/* Warehouse.get_global_image (:966-1040) for all B envs, from the engine's current state, into a DEVICE array of the caller's — the
+ * global-state input of a centralised critic, without a host visit.
+ *   layers:       n_layers values of rw_image_layer (1 .. 8, duplicates allowed), copied by value at the call
+ *   pad_to_shape: NULL, or {C', H', W'} with C' >= n_layers, H' >= grid_h, W' >= grid_w; zero padding split as :1029-1033
+ *                 (before = d / 2, after = d - d / 2, on all three axes)
+ *   elem:         0 float32, 1 uint8 (every element is an integer in 0 .. 4)
+ *   out_dev:      [B][C'][H'][W'] of that element type, any alignment of the element type; every element is written, the padding
+ *                 zeros included, and nothing else
+ * Layers: SHELVES, AGENTS, GOALS 0 / 1; ACCESSIBLE 1 except under an agent; REQUESTS 1 at the cells of the queued shelves (a carried
+ * requested shelf lies under its carrier); AGENT_DIRECTION (dir + 1) and AGENT_LOAD (1 for an agent that carries a shelf) are written as
+ * the reference writes them, `layer[ag.x, ag.y]` on an (H, W) array (:1003, :1008): on the mirrored cell, the highest agent index winning
+ * a shared one.  Where the reference raises IndexError there (x >= grid_h or y >= grid_w; AGENT_LOAD: of a carrying agent) that agent
+ * writes nothing and the next rw_sync returns RW_ERR_INDEX, as for the IMAGE observations.
+ * Asynchrony: the call ONLY ENQUEUES one kernel on the engine's stream — no host synchronisation, no allocation, no host-to-device copy
+ *   (the layer list and the shape travel in the kernel's arguments), no derived view is refreshed: the kernel reads the shelf layer, the
+ *   packed agent records and the queue as the step kernels keep them.  It is therefore legal while that stream is being captured into a
+ *   HIP graph and is replayed with the graph.  The image describes the state RW_BUF_OBS describes at that point of the stream (after a
+ *   SAME_STEP autoreset the reset state, after a NEXT_STEP termination the terminal state).  Any engine: every observation type and flag.
+ * Errors: RW_ERR_INVALID_ARG for a NULL engine / layers / out_dev, n_layers outside 1 .. 8, a layer outside 0 .. 6, a pad dimension
+ *   smaller than the image, elem other than 0 / 1, a float32 out_dev that is not 4-byte aligned, and for an image of more than 2^30
+ *   elements per env ("slice it": smaller padding, or fewer layers per call). */
+int rw_global_image(rw_engine *eng, const int32_t *layers, int32_t n_layers, const int32_t *pad_to_shape, int32_t elem, void *out_dev);
 
 /* wait for everything enqueued; returns RW_ERR_INVALID_ACTION if any step since the last
  * rw_sync saw an out-of-range action (that action was executed as NOOP), else RW_OK */

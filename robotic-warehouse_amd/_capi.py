@@ -88,7 +88,7 @@ EXPORTS = (
     "rw_recalc_grid", "rw_get_info", "rw_seed_state", "rw_event_record", "rw_event_elapsed_ms",
     "rw_abi_version", "rw_debug_timeline", "rw_debug_store_floor", "rw_device_malloc", "rw_device_free", "rw_copy_to_device",
     "rw_copy_to_host", "rw_selftest", "rw_snapshot_create", "rw_snapshot_save", "rw_snapshot_restore", "rw_snapshot_destroy",
-    "rw_seed_device", "rw_reset_device",
+    "rw_seed_device", "rw_reset_device", "rw_global_image",
 )
 
 _libs = {}
@@ -142,6 +142,7 @@ def load(path: str | None = None):
     lib.rw_step_tape_device_timed.argtypes = [vp, vp, i32, i32, i32, i32, i32]
     lib.rw_refresh_obs.argtypes = [vp]
     lib.rw_unpack_obs.argtypes = [vp, vp, vp, C.c_int64]
+    lib.rw_global_image.argtypes = [vp, C.POINTER(i32), i32, C.POINTER(i32), i32, vp]
     lib.rw_refresh_grid.argtypes = [vp]
     lib.rw_mark_views_stale.argtypes = [vp]
     lib.rw_set_stream.argtypes = [vp, vp]
@@ -352,6 +353,14 @@ class Engine:
             self.arena_allocations += 1
         return ent[0]
 
+    def scratch(self, name, nbytes):
+        """A device array of at least `nbytes` from the engine's arena (grow-only, kept until release_arena() / close()); a c_void_p."""
+        return self._arena_buf(name, nbytes)
+
+    def read_scratch(self, name, host_array):
+        """Copies the front of arena buffer `name` into the contiguous `host_array` (waits for the engine's stream)."""
+        self._check(self.lib.rw_copy_to_host(self._h, host_array.ctypes.data, self._arena[name][0], host_array.nbytes))
+
     def snapshot(self, into=None):
         """Device-resident copy of the whole env state (see rw_snapshot_*); returns an opaque handle."""
         h = into
@@ -419,6 +428,17 @@ class Engine:
     def unpack_obs_device(self, packed_ptr, out_ptr, n_rows):
         """rw_unpack_obs: `n_rows` packed rows (device uint32 [n_rows][PW]) -> float32 [n_rows][L] at `out_ptr`, on the engine's stream."""
         self._check(self.lib.rw_unpack_obs(self._h, C.c_void_p(int(packed_ptr)), C.c_void_p(int(out_ptr)), int(n_rows)))
+
+    def global_image(self, layers, out_ptr, pad_to_shape=None, dtype=np.float32):
+        """rw_global_image: Warehouse.get_global_image of every env, built on the device from the engine's current state into the DEVICE array
+        at `out_ptr` — [B][C'][H'][W'] float32 or uint8 (`dtype`), (C', H', W') = `pad_to_shape` or (len(layers), H, W).  Enqueue only (no
+        synchronisation, no copy: legal inside a stream capture); an agent the reference would raise IndexError for shows at the next sync()."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError("a global image is float32 or uint8")
+        ls = (C.c_int32 * len(layers))(*[int(l) for l in layers])
+        pad = None if pad_to_shape is None else (C.c_int32 * 3)(*[int(v) for v in pad_to_shape])
+        self._check(self.lib.rw_global_image(self._h, ls, len(layers), pad, 0 if dt == np.float32 else 1, C.c_void_p(int(out_ptr))))
 
     def device_array(self, name, dtype=None) -> DeviceArray:
         """`dtype`: present the buffer as another dtype of the same width ("obs_packed" as int32 for torch, whose uint32 has no shift ops)."""

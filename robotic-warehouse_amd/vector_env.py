@@ -283,6 +283,7 @@ class WarehouseVecEnv(_VectorEnvBase):
         self.n_shelves = self.engines[0].S
         self._make_spaces()
         self._tviews = {}
+        self._global_images = {}  # global_image_device (output="torch"): (layers, shape, dtype) -> the tensors it allocated, one per device
         self._live_actions = None
         self._pool = None
         self._multi = None
@@ -943,6 +944,63 @@ class WarehouseVecEnv(_VectorEnvBase):
         self.global_image = global_image_from_state(st, self.goals, image_layers, pad_to_shape)
         return self.global_image
 
+    def global_image_device(self, image_layers=(ImageLayer.SHELVES, ImageLayer.GOALS), pad_to_shape=None, dtype="float32", out=None):
+        """get_global_image built ON THE DEVICE (rw_global_image): the same image, layer for layer — (B, C, H, W), or (B,) + pad_to_shape —
+        as float32 or uint8 (`dtype`; every element is an integer in 0 .. 4), from the state the current observation describes.  One
+        kernel on the env's stream, which reads what the step kernels keep: no get_state(), no copy of the grid, no cache (every call
+        recomputes; get_global_image and its cache are untouched).
+        output="torch": a CUDA tensor, allocated on the first call per (layers, shape, dtype) and overwritten in place by later ones — or
+        `out`, a contiguous CUDA tensor of that shape and dtype (a slice at any element offset will do).  Nothing waits and nothing
+        visits the host, so a policy inside capture_loop may call it (into a preallocated `out`); the reference's IndexError for the
+        AGENT_DIRECTION / AGENT_LOAD layers (an agent at x >= H or y >= W) surfaces at the next sync(), and such an agent writes nothing.
+        A sharded env returns one tensor per device (`out`: one per device).
+        numpy output: the same kernel into a device scratch array of the engine's, then sync() — IndexError where the reference raises
+        it — and a host array gathered over the shards.
+        AssertionError for a pad_to_shape smaller than the image (:1028), ValueError for an unknown layer (:1018)."""
+        layers = tuple(ImageLayer(enum_value(l)).value for l in image_layers)
+        if not 1 <= len(layers) <= 8:
+            raise ValueError("global_image_device takes 1 to 8 image layers")
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError('dtype must be "float32" or "uint8"')
+        shape = (len(layers),) + tuple(self.grid_size)
+        if pad_to_shape is not None:
+            pad_to_shape = tuple(int(v) for v in pad_to_shape)
+            assert len(pad_to_shape) == 3 and all(p >= s for p, s in zip(pad_to_shape, shape))
+            shape = pad_to_shape
+        if self.output == "torch":
+            t = self._torch
+            tdt = t.float32 if dt == np.float32 else t.uint8
+            outs = self._global_images.get((layers, shape, dt.str)) if out is None else list(out) if isinstance(out, (list, tuple)) else [out]
+            if outs is None:
+                outs = self._global_images[(layers, shape, dt.str)] = [
+                    t.empty((eng.B,) + shape, dtype=tdt, device=f"cuda:{dev}") for eng, dev in zip(self.engines, self.devices)]
+            if len(outs) != len(self.engines):
+                raise ValueError(f"`out` must hold one tensor per device ({len(self.engines)})")
+            for eng, dev, o in zip(self.engines, self.devices, outs):
+                if not (o.is_cuda and o.device.index == dev and o.dtype == tdt and tuple(o.shape) == (eng.B,) + shape and o.is_contiguous()):
+                    raise ValueError(f"`out` must be a contiguous {tdt} CUDA tensor of shape {(eng.B,) + shape} on device {dev}")
+            for eng, o in zip(self.engines, outs):
+                eng.global_image(layers, o.data_ptr(), pad_to_shape, dt)
+            self._live_global_image = outs  # (a caller's `out` stays alive until the next call: the launch is only enqueued)
+            return outs[0] if len(outs) == 1 else tuple(outs)
+        if out is not None:
+            raise ValueError('`out` is a device tensor: it exists with output="torch" only')
+        parts = [np.empty((eng.B,) + shape, dt) for eng in self.engines]
+        for eng, part in zip(self.engines, parts):
+            eng.global_image(layers, eng.scratch("global_image", part.nbytes).value, pad_to_shape, dt)
+        err = None
+        for eng in self.engines:  # IndexError where the reference's get_global_image raises it — after EVERY shard has been waited for, so
+            try:                  # that no shard keeps a raised flag for a later call
+                eng.sync()
+            except (IndexError, ValueError) as e:
+                err = err or e
+        if err is not None:
+            raise err
+        for eng, part in zip(self.engines, parts):
+            eng.read_scratch("global_image", part)
+        return parts[0] if len(parts) == 1 else np.concatenate(parts, axis=0)
+
     def close(self, **kwargs):
         if self._multi is not None:
             self._multi.close()
@@ -951,6 +1009,7 @@ class WarehouseVecEnv(_VectorEnvBase):
             eng.close()
         self.engines = []
         self._tviews = {}
+        self._global_images = {}
         self._fast = None          # (the fast path of step() holds the raw engine handle and views of the freed slab)
         self._fast_ok = False
         self._live_actions = None
