@@ -42,7 +42,10 @@ extern "C" {
  * Still 4, a compatible addition: two entry points, rw_seed_device and rw_reset_device (seeding and masked reset from DEVICE arrays,
  * enqueue only); no struct, flag or buffer kind changes, rw_reset itself is unchanged.
  * Still 4, a compatible addition: one entry point, rw_global_image (Warehouse.get_global_image built on the device into an array of the
- * caller's, enqueue only); no struct, flag or buffer kind changes (RW_BUF_KIND_COUNT stays 29). */
+ * caller's, enqueue only); no struct, flag or buffer kind changes (RW_BUF_KIND_COUNT stays 29).
+ * Still 4, a compatible addition: RW_TIME_LIMIT_TRUNCATES in rw_stream_flags (RW_BUF_TRUNCATED becomes live with it; no new buffer kind,
+ * RW_BUF_KIND_COUNT stays 29), bit 3 of rw_info.stats, and two entry points, rw_step_many_device2 and rw_read_outputs2 (their namesakes
+ * plus the truncated flags); rw_info keeps its size, rw_step_many_device and rw_read_outputs are unchanged. */
 #define RW_ABI_VERSION 4
 
 typedef struct rw_engine rw_engine;
@@ -219,7 +222,27 @@ enum rw_stream_flags {
      * RW_JIT_FORCE) rw_create compiles an exact-shape uint8 build through hipRTC at construction (rw_info.jit says which happened).
      * Combines with RW_STATS_ON, RW_EPISODES_ON, RW_ACTION_MASK_ON and msg_bits.  RW_PIPE_ON | RW_OBS_IMAGE_U8: the classic kernel runs
      * and rw_jit_log() says so. */
-    RW_OBS_IMAGE_U8 = 8192
+    RW_OBS_IMAGE_U8 = 8192,
+    /* Time-limit ends reported as truncation.  The reference reports every end of an episode as `terminated` and never sets `truncated`
+     * (rware/warehouse.py:935-942); a learner that bootstraps needs the two apart: reaching max_steps is no property of the state.  Per env
+     * and step, after the counters are updated (:929-933), let
+     *   by_inactivity = max_inactivity_steps != 0 && inactive >= max_inactivity_steps
+     *   by_steps      = max_steps != 0 && steps >= max_steps
+     *   done          = by_inactivity || by_steps              (the reference's `done`, unchanged)
+     * Without the flag: terminated = done, truncated = 0, and RW_BUF_TRUNCATED is stored by resets only.  With RW_TIME_LIMIT_TRUNCATES, for
+     * an env the launch stepped: terminated = by_inactivity, truncated = by_steps — both set when both rules fire on the same step
+     * (Gymnasium's TimeLimit: truncation does not look at termination) — so terminated | truncated == done on every env and every step.
+     * Everything that means "the episode ended" keeps following `done`: the pending NEXT_STEP reset, the SAME_STEP in-step reset with
+     * RW_BUF_FINAL_OBS / RW_BUF_FINAL_FEATURES, the RW_EPISODES_ON record, the terminal branch of the event counters.  A NEXT_STEP reset
+     * step (action ignored) writes 0 / 0; rw_reset / rw_reset_device, masked or not, clear both flags of the envs they reset and leave the
+     * others alone; under RW_AUTORESET_DISABLED a finished env that keeps being stepped gets its flags by the same two rules on every
+     * step.  A fused rollout leaves its last step's flags in RW_BUF_TRUNCATED, or every step's in the tape of rw_step_many_device2.
+     * RW_BUF_TRUNCATED stays read-only for rw_write.  Off by default: the default is the reference's behaviour, bit for bit.
+     * Which kernels run with it: as for RW_STATS_ON / RW_EPISODES_ON / RW_ACTION_MASK_ON (the same compile switch carries the code) — the
+     * generic kernel below 4096 envs, with RW_JIT_OFF or without hipRTC, else an exact-shape build compiled at construction; rw_jit_log
+     * says so.  Combines with every other flag, with msg_bits and the IMAGE types.  RW_PIPE_ON | RW_TIME_LIMIT_TRUNCATES: the classic
+     * kernel runs and rw_jit_log() says so.  Out of scope: max_inactivity_steps as a truncation; the pipelined (PIPE=1) kernels. */
+    RW_TIME_LIMIT_TRUNCATES = 16384
 };
 
 /* Device buffers (all env-major, C-contiguous).  Replaces the attributes callers read off the
@@ -232,7 +255,8 @@ enum rw_buffer_kind {
                                                    with RW_OBS_IMAGE_U8                           */
     RW_BUF_REWARDS = 1,      /* float32 [B][N]                                                    */
     RW_BUF_TERMINATED = 2,   /* uint8   [B]        `done` (:935-941)                              */
-    RW_BUF_TRUNCATED = 3,    /* uint8   [B]        always 0 (:942); read-only (rw_write refuses it) */
+    RW_BUF_TRUNCATED = 3,    /* uint8   [B]        always 0 (:942) — with RW_TIME_LIMIT_TRUNCATES: the step limit ended
+                                                   the episode; read-only (rw_write refuses it)   */
     RW_BUF_GRID = 4,         /* int32   [B][2][H][W] layer 0 agent ids, layer 1 shelf ids (:11-14).
                                                    A DERIVED VIEW: rebuilt from the state the kernels keep (shelf
                                                    layer, agent coordinates) by rw_read / rw_get_buffer of this kind
@@ -389,6 +413,11 @@ int rw_step_tape_device_timed(rw_engine *eng, const int32_t *tape_dev, int32_t t
  * outputs ([T][B][N][L] f32, [T][B][N] f32, [T][B] u8); otherwise only the last step's remain. */
 int rw_step_many_device(rw_engine *eng, const int32_t *actions_dev, int32_t n_steps,
                         float *obs_tape, float *reward_tape, uint8_t *terminated_tape);
+/* rw_step_many_device plus the truncated flags: `truncated_tape`, if non-NULL, is a device pointer to uint8 [T][B] and receives every
+ * step's flag (RW_TIME_LIMIT_TRUNCATES; otherwise only the last step's remains, in RW_BUF_TRUNCATED).  On an engine without the flag the
+ * tape is zero-filled by an asynchronous memset on the engine's stream: enqueue only, legal under stream capture. */
+int rw_step_many_device2(rw_engine *eng, const int32_t *actions_dev, int32_t n_steps,
+                         float *obs_tape, float *reward_tape, uint8_t *terminated_tape, uint8_t *truncated_tape);
 
 /* One call that enqueues a step on SEVERAL engines — the shards of a single-process multi-device env (one engine per GPU).  When
  * every engine sits on a device of its own, every engine but the first is launched by a thread that rw_multi_create starts
@@ -465,6 +494,8 @@ int rw_read(rw_engine *eng, int kind, void *host_dst, size_t bytes);
  * back to back, one synchronisation; any pointer may be NULL (skipped).  `truncated` is always False (:942): nothing to read.
  * (RW_OBS_IMAGE_U8: `obs` receives the buffer's B * N * obs_length BYTES through the same pointer.) */
 int rw_read_outputs(rw_engine *eng, float *obs, float *rewards, uint8_t *terminated, float *features);
+/* rw_read_outputs plus RW_BUF_TRUNCATED (B bytes; all 0 without RW_TIME_LIMIT_TRUNCATES), still one synchronisation */
+int rw_read_outputs2(rw_engine *eng, float *obs, float *rewards, uint8_t *terminated, uint8_t *truncated, float *features);
 int rw_write(rw_engine *eng, int kind, const void *host_src, size_t bytes);
 /* rebuild RW_BUF_GRID exactly like Warehouse._recalc_grid (:749-755) from explicit shelf
  * positions (host int32 [B][S][2] = (x,y) per shelf id; later ids overwrite earlier) and the
@@ -510,7 +541,7 @@ typedef struct rw_info {
                                   same, read from the disk cache; -1: run-time specialisation was tried and is not in use (rw_jit_log) */
     int64_t engine_bytes_per_env_step; /* bytes this engine's state layout has to move per env-step: shelf shadow (1 or 2 B per
                                   cell) + packed agent records r/w + actions + queue + counters / flags + observation + rewards +
-                                  terminated (+ messages r/w, IMAGE_DICT features; RW_EPISODES_ON: running return and length r/w; RW_ACTION_MASK_ON: N bytes).  The PMC traffic of a step is checked against
+                                  terminated (+ messages r/w, IMAGE_DICT features; RW_EPISODES_ON: running return and length r/w; RW_ACTION_MASK_ON: N bytes; RW_TIME_LIMIT_TRUNCATES: truncated, 1 byte).  The PMC traffic of a step is checked against
                                   it; bench.py prices `frac_engine` on it (<= 1 by construction)                               */
     int32_t stagger_ticks;     /* > 0: the k-th of the first eight workgroups a CU receives starts k * stagger_ticks * 10 ns late, so that
                                   the workgroups of a CU do not run their load / agent / store phases in lock-step.  rw_create's measured rule,
@@ -522,7 +553,7 @@ typedef struct rw_info {
                                   same value.  A delay, never a different result */
     int32_t pipe_envs_per_workgroup; /* != 0: rw_step* launches run the chunk-pipelined persistent build with chunks of this many envs ... */
     int32_t pipe_workgroups;         /* ... on this many persistent workgroups (rw_stream_flags RW_PIPE_ON / RW_PIPE_OFF)              */
-    int32_t stats;                   /* a bit set: bit 0 RW_STATS_ON — RW_BUF_STAT_* are kept; bit 1 RW_EPISODES_ON — RW_BUF_EP_* are kept; bit 2 RW_ACTION_MASK_ON — RW_BUF_ACTION_MASK is written
+    int32_t stats;                   /* a bit set: bit 0 RW_STATS_ON — RW_BUF_STAT_* are kept; bit 1 RW_EPISODES_ON — RW_BUF_EP_* are kept; bit 2 RW_ACTION_MASK_ON — RW_BUF_ACTION_MASK is written; bit 3 RW_TIME_LIMIT_TRUNCATES — RW_BUF_TRUNCATED is live
                                         (an engine with only RW_STATS_ON reads 1, as before; was `reserved[1]`: same struct size)      */
     int32_t obs_packed;              /* 1: RW_OBS_PACKED — the launches write RW_BUF_OBS_PACKED, RW_BUF_OBS is empty; engine_bytes_per_env_step
                                         prices the packed row (appended with ABI 4).  2: RW_OBS_IMAGE_U8 — the elements of RW_BUF_OBS are

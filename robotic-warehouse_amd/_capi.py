@@ -56,6 +56,7 @@ RW_OBS_PACKED = 1024  # rw_stream_flags: bit-packed FLATTENED observations — u
 RW_EPISODES_ON = 2048  # rw_stream_flags: keep per-episode return / length on the device, RW_BUF_EP_RETURN .. _EP_COUNT (off by default)
 RW_ACTION_MASK_ON = 4096  # rw_stream_flags: the step kernels write a valid-action byte per agent to RW_BUF_ACTION_MASK (off by default)
 RW_OBS_IMAGE_U8 = 8192  # rw_stream_flags: IMAGE / IMAGE_DICT observations as uint8 — "obs" keeps its shape, one byte per element
+RW_TIME_LIMIT_TRUNCATES = 16384  # rw_stream_flags: reaching max_steps sets `truncated`, only max_inactivity_steps `terminated` (off by default: the reference's `terminated` = done)
 RW_STATS_ON = 128  # rw_stream_flags: keep the per-env event counters RW_BUF_STAT_DELIVERIES / _FAILED_MOVES (off by default)
 
 AUTORESET = {"disabled": 0, None: 0, "next_step": 1, "same_step": 2}
@@ -88,7 +89,7 @@ EXPORTS = (
     "rw_recalc_grid", "rw_get_info", "rw_seed_state", "rw_event_record", "rw_event_elapsed_ms",
     "rw_abi_version", "rw_debug_timeline", "rw_debug_store_floor", "rw_device_malloc", "rw_device_free", "rw_copy_to_device",
     "rw_copy_to_host", "rw_selftest", "rw_snapshot_create", "rw_snapshot_save", "rw_snapshot_restore", "rw_snapshot_destroy",
-    "rw_seed_device", "rw_reset_device", "rw_global_image",
+    "rw_seed_device", "rw_reset_device", "rw_global_image", "rw_step_many_device2", "rw_read_outputs2",
 )
 
 _libs = {}
@@ -138,6 +139,7 @@ def load(path: str | None = None):
     lib.rw_step.argtypes = [vp, vp]
     lib.rw_step_device.argtypes = [vp, vp]
     lib.rw_step_many_device.argtypes = [vp, vp, i32, vp, vp, vp]
+    lib.rw_step_many_device2.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     lib.rw_step_tape_device.argtypes = [vp, vp, i32, i32, i32]
     lib.rw_step_tape_device_timed.argtypes = [vp, vp, i32, i32, i32, i32, i32]
     lib.rw_refresh_obs.argtypes = [vp]
@@ -159,6 +161,7 @@ def load(path: str | None = None):
     lib.rw_get_buffer.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
     lib.rw_read.argtypes = [vp, C.c_int, vp, C.c_size_t]
     lib.rw_read_outputs.argtypes = [vp, vp, vp, vp, vp]
+    lib.rw_read_outputs2.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.rw_write.argtypes = [vp, C.c_int, vp, C.c_size_t]
     lib.rw_recalc_grid.argtypes = [vp, vp, i32]
     lib.rw_get_info.argtypes = [vp, C.POINTER(RwInfo)]
@@ -217,7 +220,7 @@ class Engine:
                  max_inactivity_steps, max_steps, reward_type, normalised_coordinates=False,
                  autoreset_mode="next_step", device_id=0, envs_per_workgroup=0,
                  threads_per_workgroup=0, stream=None, library=None, observation_type=1,
-                 image_layers=(), image_directional=True, msg_bits=0, use_given_stream=False, obs_stores=None, jit=None, pipe=None, stats=False, wave_priority=None, obs_packed=False, episodes=False, action_mask=False, obs_image_u8=False):
+                 image_layers=(), image_directional=True, msg_bits=0, use_given_stream=False, obs_stores=None, jit=None, pipe=None, stats=False, wave_priority=None, obs_packed=False, episodes=False, action_mask=False, obs_image_u8=False, time_limit_truncates=False):
         self.lib = load(library)
         self._h = C.c_void_p()
         self._arena, self.arena_allocations = {}, 0  # rollout_host's device tapes (grow-only; freed in close())
@@ -235,6 +238,7 @@ class Engine:
             | {None: 0, "auto": 0, False: RW_PIPE_OFF, "off": RW_PIPE_OFF, True: RW_PIPE_ON, "on": RW_PIPE_ON}[pipe]
             | (RW_STATS_ON if stats else 0) | (RW_OBS_PACKED if obs_packed else 0) | (RW_EPISODES_ON if episodes else 0)
             | (RW_ACTION_MASK_ON if action_mask else 0) | (RW_OBS_IMAGE_U8 if obs_image_u8 else 0)
+            | (RW_TIME_LIMIT_TRUNCATES if time_limit_truncates else 0)
             | {None: 0, "auto": 0, False: RW_PRIO_OFF, "off": RW_PRIO_OFF, True: RW_PRIO_ON, "on": RW_PRIO_ON}[wave_priority],
             hw.ctypes.data, goals.ctypes.data, C.c_void_p(stream or 0))
         rc = self.lib.rw_create(C.byref(cfg), C.byref(self._h))
@@ -253,6 +257,7 @@ class Engine:
         self.stats = bool(i.stats & 1)      # rw_info.stats is a bit set: bit 0 RW_STATS_ON, bit 1 RW_EPISODES_ON
         self.episodes = bool(i.stats & 2)
         self.action_mask = bool(i.stats & 4)  # bit 2 RW_ACTION_MASK_ON
+        self.time_limit_truncates = bool(i.stats & 8)  # bit 3 RW_TIME_LIMIT_TRUNCATES: "truncated" is live
         # obs_packed=True (RW_OBS_PACKED): the launches write uint32 rows of PW words to "obs_packed"; "obs" does not exist
         self.packed = i.obs_packed == 1
         # obs_image_u8=True (RW_OBS_IMAGE_U8, rw_info.obs_packed == 2): "obs" holds uint8 elements — this engine's dtype of that row
@@ -315,14 +320,15 @@ class Engine:
         self._check(self.lib.rw_step_tape_device_timed(self._h, C.c_void_p(int(tape_ptr)), int(tape_steps), int(first),
                                                        int(n_steps), int(start_slot), int(stop_slot)))
 
-    def step_many_device(self, dev_ptr, n_steps, obs_tape=0, reward_tape=0, terminated_tape=0):
-        self._check(self.lib.rw_step_many_device(self._h, C.c_void_p(int(dev_ptr)), int(n_steps),
-                                                 C.c_void_p(int(obs_tape)), C.c_void_p(int(reward_tape)),
-                                                 C.c_void_p(int(terminated_tape))))
+    def step_many_device(self, dev_ptr, n_steps, obs_tape=0, reward_tape=0, terminated_tape=0, truncated_tape=0):
+        """`truncated_tape`: uint8 [T][B] on the device — every step's flag with time_limit_truncates, zeros without (rw_step_many_device2)."""
+        self._check(self.lib.rw_step_many_device2(self._h, C.c_void_p(int(dev_ptr)), int(n_steps),
+                                                  C.c_void_p(int(obs_tape)), C.c_void_p(int(reward_tape)),
+                                                  C.c_void_p(int(terminated_tape)), C.c_void_p(int(truncated_tape))))
 
     def rollout_host(self, actions, want_obs=True):
         """`T` fused steps (one launch) from a host action tape (T, B, N); returns host tapes
-        (obs (T,B,N,L) or None, rewards (T,B,N), terminated (T,B))."""
+        (obs (T,B,N,L) or None, rewards (T,B,N), terminated (T,B)) — and truncated (T,B) as a fourth with time_limit_truncates."""
         a = np.ascontiguousarray(actions, dtype=np.int32).reshape(-1, self.B, self.N * (1 + self.M))
         T = a.shape[0]
         obs = np.empty((T,) + self.shapes[self.obs_name], self.dtypes[self.obs_name]) if want_obs else None  # (packed: uint32 (T,B,N,PW))
@@ -334,11 +340,16 @@ class Engine:
         self._check(self.lib.rw_copy_to_device(self._h, d_a, a.ctypes.data, a.nbytes))
         d_o = self._arena_buf("obs", obs.nbytes) if want_obs else C.c_void_p(0)
         d_r, d_t = self._arena_buf("rewards", rew.nbytes), self._arena_buf("terminated", term.nbytes)
-        self._check(self.lib.rw_step_many_device(self._h, d_a, T, d_o, d_r, d_t))
+        trunc = np.empty((T, self.B), np.uint8) if self.time_limit_truncates else None
+        d_u = self._arena_buf("truncated", trunc.nbytes) if trunc is not None else C.c_void_p(0)
+        self._check(self.lib.rw_step_many_device2(self._h, d_a, T, d_o, d_r, d_t, d_u))
         if want_obs:
             self._check(self.lib.rw_copy_to_host(self._h, obs.ctypes.data, d_o, obs.nbytes))
         self._check(self.lib.rw_copy_to_host(self._h, rew.ctypes.data, d_r, rew.nbytes))
         self._check(self.lib.rw_copy_to_host(self._h, term.ctypes.data, d_t, term.nbytes))
+        if trunc is not None:
+            self._check(self.lib.rw_copy_to_host(self._h, trunc.ctypes.data, d_u, trunc.nbytes))
+            return obs, rew, term, trunc
         return obs, rew, term
 
     def _arena_buf(self, name, nbytes):
@@ -409,17 +420,19 @@ class Engine:
         self._check(self.lib.rw_read(self._h, BUF[name], out.ctypes.data, out.nbytes))
         return out
 
-    def read_outputs(self, want_features=False):
-        """obs, rewards, terminated (uint8), features-or-None as fresh host arrays: one C call, one synchronisation."""
+    def read_outputs(self, want_features=False, want_truncated=False):
+        """obs, rewards, terminated (uint8), features-or-None as fresh host arrays: one C call, one synchronisation.  `want_truncated`:
+        truncated (uint8) as a fifth element, in the same round trip (rw_read_outputs2)."""
         obs = None if self.packed else np.empty(self.shapes["obs"], self.dtypes["obs"])
         rew = np.empty(self.shapes["rewards"], np.float32)
         term = np.empty(self.shapes["terminated"], np.uint8)
         feat = np.empty(self.shapes["features"], np.float32) if want_features else None
-        self._check(self.lib.rw_read_outputs(self._h, None if self.packed else obs.ctypes.data, rew.ctypes.data, term.ctypes.data,
-                                             feat.ctypes.data if want_features else None))
+        trunc = np.empty(self.shapes["truncated"], np.uint8) if want_truncated else None
+        self._check(self.lib.rw_read_outputs2(self._h, None if self.packed else obs.ctypes.data, rew.ctypes.data, term.ctypes.data,
+                                              trunc.ctypes.data if want_truncated else None, feat.ctypes.data if want_features else None))
         if self.packed:  # (rw_read_outputs speaks float32: the packed rows are 1 / 18 of them, one more small copy)
             obs = self.read("obs_packed")
-        return obs, rew, term, feat
+        return (obs, rew, term, feat, trunc) if want_truncated else (obs, rew, term, feat)
 
     def write(self, name, array):
         a = np.ascontiguousarray(array, dtype=self.dtypes[name]).reshape(self.shapes[name])

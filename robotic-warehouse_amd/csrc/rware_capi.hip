@@ -65,7 +65,7 @@ struct Pipe {
 };
 
 // The opt-in outputs (rw_engine::features): one bit per switch of rw_stream_flags, each described once in kFeatures below
-enum : uint32_t { F_STATS = 1, F_EPISODES = 2, F_MASK = 4, F_PACKED = 8, F_IMAGE_U8 = 16 };  // (the first three: the bits of rw_info::stats)
+enum : uint32_t { F_STATS = 1, F_EPISODES = 2, F_MASK = 4, F_TRUNC = 8, F_PACKED = 16, F_IMAGE_U8 = 32 };  // (the first four: the bits of rw_info::stats)
 
 // What a buffer kind is (kKinds below): a derived view — one of a group that refresh() unpacks from what the step kernels keep and pack()
 // packs back after a host write; the groups in the order rw_refresh_grid rebuilds them —, simulation state (part of a snapshot), or an input / output
@@ -413,8 +413,8 @@ int launch(rw_engine *eng, rw::LaunchArgs la, int op, bool rollout = false, hipE
     }
     if (k.jit) {  // a run-time specialised build: the same launch through the module API
         const rw::Params *cp = eng->d_prm;
-        void *args[13] = {&cp, &la.actions, &la.op, &la.n_steps, &la.obs, &la.rewards, &la.terminated, &la.reset_mask, &la.timeline,
-                          &la.act_stride, &la.obs_stride, &la.rew_stride, &la.term_stride};
+        void *args[15] = {&cp, &la.actions, &la.op, &la.n_steps, &la.obs, &la.rewards, &la.terminated, &la.reset_mask, &la.timeline,
+                          &la.act_stride, &la.obs_stride, &la.rew_stride, &la.term_stride, &la.truncated, &la.trunc_stride};
         if (start || stop)
             RW_HIP(eng, hipExtModuleLaunchKernel(k.jit, (uint32_t)k.n_wg * (uint32_t)eng->T, 1, 1, (uint32_t)eng->T, 1, 1, k.lds, eng->stream,
                                                  args, nullptr, start, stop, 0));
@@ -533,6 +533,8 @@ constexpr Feature kFeatures[] = {
     {F_STATS, RW_STATS_ON, rw::OP_FLAG_STATS, true, true, 0, 0, "RW_STATS_ON", "event counters", "the counting code"},
     {F_EPISODES, RW_EPISODES_ON, rw::OP_FLAG_EPISODES, true, false, 8, 8, "RW_EPISODES_ON", "episode statistics", "the code (RW_STATS_BUILD)"},
     {F_MASK, RW_ACTION_MASK_ON, rw::OP_FLAG_MASK, true, false, 1, 0, "RW_ACTION_MASK_ON", "action masks", "the code (RW_STATS_BUILD)"},
+    // (no buffer of its own: RW_BUF_TRUNCATED exists anyway; one more byte per env is written)
+    {F_TRUNC, RW_TIME_LIMIT_TRUNCATES, rw::OP_FLAG_TRUNC, true, false, 0, 1, "RW_TIME_LIMIT_TRUNCATES", "time-limit truncation", "the code (RW_STATS_BUILD)"},
 };
 constexpr uint32_t features_where(bool Feature::*column, bool value) {
     uint32_t set = 0;
@@ -554,7 +556,7 @@ void jit_note(rw_engine *eng, const std::string &text) { eng->jit_log += (eng->j
 // One row per RW_BUF_* kind, indexed by kind: element size; elements per env; what it exists with (an absent buffer is empty); its role; and,
 // where rw_write refuses it, why.  (exists with: always; a feature, F_*; the float rows, i.e. not F_PACKED; SAME_STEP autoreset; SAME_STEP with IMAGE_DICT)
 enum Extent : uint8_t { X_1, X_N, X_NL, X_NPW, X_2HW, X_Q, X_6, X_NAM, X_6N };  // 1, N, N L, N PW, 2 H W, Q, 6, N (1 + M), 6 N
-enum : uint8_t { W_ALWAYS = 0, W_FLOAT_ROWS = 16, W_FINAL, W_FINAL_DICT };
+enum : uint8_t { W_ALWAYS = 0, W_FLOAT_ROWS = 64, W_FINAL, W_FINAL_DICT };  // (beyond every F_*)
 struct Kind { int kind; const char *name; uint8_t elem; Extent ext; uint8_t with; Role role; const char *read_only = nullptr; };
 #define K(kind, ...) {RW_BUF_##kind, "RW_BUF_" #kind, __VA_ARGS__}
 constexpr Kind kKinds[] = {
@@ -1235,6 +1237,8 @@ int fill_params(rw_engine *eng, const rw_config *cfg, const Shape &s) {
     la.op = rw::OP_STEP;
     la.n_steps = 1;
     la.act_stride = la.obs_stride = la.rew_stride = la.term_stride = 0;
+    la.truncated = at<uint8_t>(eng, RW_BUF_TRUNCATED);  // (written by OP_FLAG_TRUNC launches only)
+    la.trunc_stride = 0;
     if (hipMalloc(&eng->d_prm, sizeof(rw::Params)) != hipSuccess ||
         hipMemcpy(eng->d_prm, &eng->prm, sizeof(rw::Params), hipMemcpyHostToDevice) != hipSuccess)
         return fail(eng, RW_ERR_HIP, "uploading the parameter block failed");
@@ -1428,6 +1432,11 @@ int rw_step(rw_engine *eng, const int32_t *actions_host) {
 
 int rw_step_many_device(rw_engine *eng, const int32_t *actions_dev, int32_t n_steps, float *obs_tape,
                         float *reward_tape, uint8_t *terminated_tape) {
+    return rw_step_many_device2(eng, actions_dev, n_steps, obs_tape, reward_tape, terminated_tape, nullptr);
+}
+
+int rw_step_many_device2(rw_engine *eng, const int32_t *actions_dev, int32_t n_steps, float *obs_tape,
+                         float *reward_tape, uint8_t *terminated_tape, uint8_t *truncated_tape) {
     if (!eng || !actions_dev || n_steps < 0) return RW_ERR_INVALID_ARG;
     RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
     const size_t BN = (size_t)eng->prm.B * eng->prm.N;
@@ -1441,6 +1450,11 @@ int rw_step_many_device(rw_engine *eng, const int32_t *actions_dev, int32_t n_st
     if (obs_tape) { la.obs = obs_tape; la.obs_stride = (int64_t)(BN * eng->row_elems); }
     if (reward_tape) { la.rewards = reward_tape; la.rew_stride = (int64_t)BN; }
     if (terminated_tape) { la.terminated = terminated_tape; la.term_stride = (int64_t)eng->prm.B; }
+    if (truncated_tape) {
+        if (eng->features & F_TRUNC) { la.truncated = truncated_tape; la.trunc_stride = (int64_t)eng->prm.B; }
+        // (no RW_TIME_LIMIT_TRUNCATES: nothing truncates and no kernel writes the flag — zeros, enqueued on the stream like the launch)
+        else RW_HIP(eng, hipMemsetAsync(truncated_tape, 0, (size_t)n_steps * (size_t)eng->prm.B, eng->stream));
+    }
     return launch(eng, la, rw::OP_STEP, /*rollout=*/true);
 }
 
@@ -1781,6 +1795,10 @@ int rw_read(rw_engine *eng, int kind, void *host_dst, size_t bytes) {
 }
 
 int rw_read_outputs(rw_engine *eng, float *obs, float *rewards, uint8_t *terminated, float *features) {
+    return rw_read_outputs2(eng, obs, rewards, terminated, nullptr, features);
+}
+
+int rw_read_outputs2(rw_engine *eng, float *obs, float *rewards, uint8_t *terminated, uint8_t *truncated, float *features) {
     // what step() returns, in ONE round trip: the copies are enqueued back to back and waited for once (four rw_read calls
     // are four synchronisations — 137 us per step at B = 1024 where the kernel takes 5)
     if (!eng) return RW_ERR_INVALID_ARG;
@@ -1788,7 +1806,7 @@ int rw_read_outputs(rw_engine *eng, float *obs, float *rewards, uint8_t *termina
         return fail(eng, RW_ERR_UNSUPPORTED, "rw_read_outputs: no float32 observation with RW_OBS_PACKED (pass obs = NULL and read RW_BUF_OBS_PACKED)");
     RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
     const struct { void *dst; int kind; } parts[] = {{obs, RW_BUF_OBS}, {rewards, RW_BUF_REWARDS}, {terminated, RW_BUF_TERMINATED},
-                                                     {features, RW_BUF_FEATURES}};
+                                                     {truncated, RW_BUF_TRUNCATED}, {features, RW_BUF_FEATURES}};
     for (const auto &pt : parts)
         if (pt.dst && eng->buf[pt.kind].bytes)
             RW_HIP(eng, hipMemcpyAsync(pt.dst, eng->buf[pt.kind].ptr, eng->buf[pt.kind].bytes, hipMemcpyDeviceToHost, eng->stream));

@@ -206,6 +206,10 @@ struct LaunchArgs {
     uint64_t *timeline;         // nullptr, or [n_wg][TL_MARKS] wall-clock stamps (rw_debug_timeline)
     // Strides are in elements per step (0 == every step writes the same buffer).
     int64_t act_stride, obs_stride, rew_stride, term_stride;
+    // RW_TIME_LIMIT_TRUNCATES (launches carry OP_FLAG_TRUNC; RW_STATS_BUILD kernels only, nothing else reads the two): where the `truncated`
+    // flags go — RW_BUF_TRUNCATED, or the [T][B] tape of a fused rollout — and its stride.  Appended behind everything the other kernels read
+    uint8_t *truncated;         // [B]
+    int64_t trunc_stride;
 };
 // The kernel takes these fields as separate scalar arguments after `cp`: with
 // -amdgpu-kernarg-preload-count=16 the first 14 dwords — cp and everything up to reset_mask — arrive in
@@ -214,20 +218,21 @@ struct LaunchArgs {
     const int32_t *la_actions, const int32_t la_op, const int32_t la_n_steps, float *la_obs,               \
         float *la_rewards, uint8_t *la_terminated, const uint8_t *la_reset_mask, uint64_t *la_timeline,    \
         const int64_t la_act_stride, const int64_t la_obs_stride, const int64_t la_rew_stride,             \
-        const int64_t la_term_stride
+        const int64_t la_term_stride, uint8_t *la_truncated, const int64_t la_trunc_stride
 #define RW_LAUNCH_PARAMS_TYPES                                                                              \
     const rw::Params *, const int32_t *, const int32_t, const int32_t, float *, float *, uint8_t *, const uint8_t *,  \
-        uint64_t *, const int64_t, const int64_t, const int64_t, const int64_t
+        uint64_t *, const int64_t, const int64_t, const int64_t, const int64_t, uint8_t *, const int64_t
 #define RW_LAUNCH_ARGS(la)                                                                                  \
     (la).actions, (la).op, (la).n_steps, (la).obs, (la).rewards, (la).terminated, (la).reset_mask,         \
-        (la).timeline, (la).act_stride, (la).obs_stride, (la).rew_stride, (la).term_stride
+        (la).timeline, (la).act_stride, (la).obs_stride, (la).rew_stride, (la).term_stride, (la).truncated, (la).trunc_stride
 enum : int { OP_FLAG_TIMELINE = 0x100,
              OP_FLAG_STATS = 0x200,    // count deliveries / failed moves into Params::stat_* (see count_events, rware_phase_goals.h)
              OP_FLAG_PRIO = 0x400,     // raise the wavefronts' priority until the agent phases are done (see the kernel's prologue)
              OP_FLAG_PACKED = 0x800,   // `obs` is uint32 [B][N][PW]: store the observation bit string as bits — in an IMAGE kernel: `obs` is uint8
                                        // [B][N][L], one byte per element (RW_PACKED_BUILD kernels only)
              OP_FLAG_EPISODES = 0x1000, // keep per-episode return / length in Params::ep_* (RW_STATS_BUILD kernels only; see ep_tick, rware_phase_goals.h)
-             OP_FLAG_MASK = 0x2000 };   // write the per-agent valid-action bytes to Params::action_mask (RW_STATS_BUILD kernels only; see action_mask_store, rware_phase_goals.h)
+             OP_FLAG_MASK = 0x2000,     // write the per-agent valid-action bytes to Params::action_mask (RW_STATS_BUILD kernels only; see action_mask_store, rware_phase_goals.h)
+             OP_FLAG_TRUNC = 0x4000 };  // a step-limit end sets `truncated`, only an inactivity end `terminated` (RW_STATS_BUILD kernels only; see done_split, rware_phase_goals.h)
 enum : int { TL_START = 0, TL_ZEROED, TL_DMA_ISSUED, TL_ENV_LOADED, TL_LOADED, TL_AGENTS, TL_RESET, TL_OBS_BITS,
              TL_OBS_STORED, TL_END,  // 10, 11: where the wavefronts ran
              TL_AG_RECORD = 12, TL_AG_CELLS, TL_AG_WINNERS, TL_AG_APPLIED, TL_AG_GOALS,  // inside the agent phases (wavefront 0)
@@ -253,6 +258,7 @@ enum : int { ENVI_STEPS = 0, ENVI_INACTIVE = 1, ENVI_RESET = 2, ENVI_DONE = 3, E
              ENVI_QDIRTY = 5,  // a request was replaced since the chunk was staged: the queue has to be written back
              ENVI_NDELIV = 6,  // deliveries of the env's latest step — written by goals_and_termination only, i.e. valid iff that step
                                // delivered (ENVI_INACTIVE == 0 behind a step); read by count_events
+             // (ENVI_DONE: non-zero iff the env's step ended its episode — 1, or with OP_FLAG_TRUNC 1 | 2 inactivity rule | 4 step limit: done_split)
              ENVI_W = 8 };
 
 RW_HD int rw_up4(int x) { return (x + 3) & ~3; }
@@ -505,7 +511,7 @@ rware_step_kernel(const Params *__restrict__ cp, RW_LAUNCH_PARAMS) {
     static_assert(!kPipe || Cfg::kE <= 64 / (Cfg::kN ? Cfg::kN : 1), "the pipelined build runs the agent phases of a chunk on ONE wavefront");
     const Params &p = *cp;  // constant per engine, device-resident, L2-warm
     const LaunchArgs la{la_actions, la_op, la_n_steps, la_obs, la_rewards, la_terminated, la_reset_mask, la_timeline,
-                        la_act_stride, la_obs_stride, la_rew_stride, la_term_stride};
+                        la_act_stride, la_obs_stride, la_rew_stride, la_term_stride, la_truncated, la_trunc_stride};
     const int op = la.op & 0xff;
     const bool tl_on = (la.op & OP_FLAG_TIMELINE) != 0;  // the flag is preloaded; la.timeline itself is fetched only when set
     // Event counters: compiled in only where RW_STATS_BUILD is set — the generic kernels and the run-time compiled builds rw_create asks for
@@ -518,6 +524,8 @@ rware_step_kernel(const Params *__restrict__ cp, RW_LAUNCH_PARAMS) {
     const bool ep_on = !kPipe && (la.op & OP_FLAG_EPISODES) != 0;
     // Valid-action masks (RW_ACTION_MASK_ON): likewise — the same switch, a preloaded flag of their own, not in the pipelined flow.
     const bool mask_on = !kPipe && (la.op & OP_FLAG_MASK) != 0;
+    // Time-limit truncation (RW_TIME_LIMIT_TRUNCATES): likewise.  Off, the kernel stores `terminated` = done and leaves `truncated` to the resets.
+    const bool trunc_on = !kPipe && (la.op & OP_FLAG_TRUNC) != 0;
 #else
     constexpr bool stats_on = false;
 #endif
@@ -735,6 +743,13 @@ rware_step_kernel(const Params *__restrict__ cp, RW_LAUNCH_PARAMS) {
     float *obs_t = la.obs + (size_t)t * la.obs_stride;
     float *rew_t = la.rewards + (size_t)t * la.rew_stride;
     uint8_t *term_t = la.terminated + (size_t)t * la.term_stride;
+#if RW_STATS_BUILD
+    // (the two arguments lie behind the preloaded ones, in a kernel-argument line no other per-step launch reads: fetched only behind the
+    //  flag, at this ONE place, so that the load sinks into the branch — fetched at the loop top by everybody it cost the other
+    //  RW_STATS_BUILD engines 1.4 % per step at small-4ag x 16384 and 2.4 % per fused-rollout step: EXPERIMENTS.md round 14)
+    uint8_t *trunc_t = nullptr;
+    if (RW_RARE(trunc_on)) trunc_t = la.truncated + (size_t)t * la.trunc_stride;
+#endif
     if (t > 0) {  // the chunk is already in LDS: recycle the scratch, roll the autoreset flags forward
         lds_barrier();  // the previous step's expansion has finished reading the bit string
         clear_scratch();

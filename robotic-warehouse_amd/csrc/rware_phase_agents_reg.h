@@ -311,6 +311,9 @@
             ev[ENVI_INACTIVE] = inact;
             ev[ENVI_STEPS] = steps;
             ev[ENVI_DONE] = done;
+#if RW_STATS_BUILD
+            if (RW_RARE(trunc_on) && done) ev[ENVI_DONE] = done_split(inact, steps);
+#endif
             if (done && k_autoreset == AR_SAME_STEP) {
                 ev[ENVI_RESET] = 1;
                 atomicOr(&s_misc[0], 1);

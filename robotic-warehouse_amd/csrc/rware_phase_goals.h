@@ -5,6 +5,15 @@
     // P5 of one env, run by its leader lane once the moves are applied (:903-942): goals in list order, request replacement
     // with the numpy-exact draw, rewards, the env's counters and termination.  ONE copy, used by both agent-phase
     // implementations below (each kernel instantiation has exactly one call site, so it is inlined there).
+#if RW_STATS_BUILD
+    // done_split (RW_STATS_BUILD kernels with RW_TIME_LIMIT_TRUNCATES): what ENVI_DONE holds for an env whose step ended its episode — bit 0
+    // `done` as ever, bit 1 the inactivity rule fired (`terminated`), bit 2 the step limit did (`truncated`).  Computed where `done` is, from
+    // the counters of that step: the reset path zeroes them before it stores the flags.  Every other reader of ENVI_DONE tests it against 0;
+    // without the flag the word stays 0 / 1.
+    auto done_split = [&](int inact, int steps) {
+        return 1 | ((k_max_inactivity && inact >= k_max_inactivity) ? 2 : 0) | ((k_max_steps && steps >= k_max_steps) ? 4 : 0);
+    };
+#endif
     auto goals_and_termination = [&](int e, int ge, int base, int32_t *ev, CellT *gS, uint8_t *gA) {
         int32_t *q = s_queue + e * Q;
         bool delivered = false;
@@ -52,6 +61,9 @@
         const int done = ((k_max_inactivity && ev[ENVI_INACTIVE] >= k_max_inactivity) ||
                           (k_max_steps && ev[ENVI_STEPS] >= k_max_steps)) ? 1 : 0;
         ev[ENVI_DONE] = done;
+#if RW_STATS_BUILD
+        if (RW_RARE(trunc_on) && done) ev[ENVI_DONE] = done_split(ev[ENVI_INACTIVE], ev[ENVI_STEPS]);
+#endif
         if (done && k_autoreset == AR_SAME_STEP) {
             ev[ENVI_RESET] = 1;
             atomicOr(&s_misc[0], 1);

@@ -176,8 +176,16 @@
             if (!ev[ENVI_RESET]) continue;
             for (int k = 0; k < Q; ++k) q_queue[(size_t)(e0 + e) * Q + k] = s_queue[e * Q + k];
             cnt_store(e0 + e, 0, 0);  // steps 0, nothing pending, inactive 0
-            term_t[e0 + e] = (uint8_t)ev[ENVI_DONE];
-            as_global(p.truncated)[e0 + e] = 0;
+#if RW_STATS_BUILD
+            if (RW_RARE(trunc_on)) {  // RW_TIME_LIMIT_TRUNCATES: the flags of the step that ended the episode (SAME_STEP; done_split), else 0 / 0
+                term_t[e0 + e] = (uint8_t)((ev[ENVI_DONE] >> 1) & 1);
+                trunc_t[e0 + e] = (uint8_t)((ev[ENVI_DONE] >> 2) & 1);
+            } else
+#endif
+            {
+                term_t[e0 + e] = (uint8_t)ev[ENVI_DONE];
+                as_global(p.truncated)[e0 + e] = 0;
+            }
 #if RW_STATS_BUILD
             if (RW_RARE(ep_on)) ep_tick_env(e, ev);
 #endif

@@ -26,10 +26,16 @@
                     //  following step consumes it from LDS)
                     const int pend = (ev[ENVI_DONE] && k_autoreset == AR_NEXT_STEP && (!kRollout || t + 1 == n_steps)) ? (int)0x80000000 : 0;
                     cnt_store(ge, ev[ENVI_STEPS] | pend, ev[ENVI_INACTIVE]);  // ONE 8-byte store: the env's counter record
+#if RW_STATS_BUILD
+                    if (RW_RARE(trunc_on)) {  // RW_TIME_LIMIT_TRUNCATES: the two rules apart (done_split), two byte streams
+                        term_t[ge] = (uint8_t)((ev[ENVI_DONE] >> 1) & 1);
+                        trunc_t[ge] = (uint8_t)((ev[ENVI_DONE] >> 2) & 1);
+                    } else
+#endif
                     term_t[ge] = (uint8_t)ev[ENVI_DONE];
-                    // Only what changed: RW_BUF_TRUNCATED is zero for the engine's lifetime (the reference never truncates,
-                    // :942); the queue changes only on a delivery.  Every store stream a step does not issue is ~0.1 us of it
-                    // (DESIGN.md ablations).
+                    // Only what changed: without RW_TIME_LIMIT_TRUNCATES RW_BUF_TRUNCATED is zero for the engine's lifetime (the
+                    // reference never truncates, :942); the queue changes only on a delivery.  Every store stream a step does not
+                    // issue is ~0.1 us of it (DESIGN.md ablations).
                     if (ev[ENVI_QDIRTY])
                         for (int k = 0; k < Q; ++k) q_queue[(size_t)ge * Q + k] = s_queue[e * Q + k];
 #if RW_STATS_BUILD

@@ -101,7 +101,8 @@ def shard_seeds(rank: int, envs_per_rank: int, seed: int = 0):
 
 def make_vec(env_id: str, num_envs: int, **kwargs):
     """`gym.make_vec(id, num_envs=B)` analogue that works without gymnasium installed.  `kwargs` go to WarehouseVecEnv — e.g.
-    obs_format="packed" for bit-packed FLATTENED observations, obs_format="uint8" for uint8 IMAGE / IMAGE_DICT observations
+    obs_format="packed" for bit-packed FLATTENED observations, obs_format="uint8" for uint8 IMAGE / IMAGE_DICT observations,
+    time_limit_truncates=True to have the registered ids' max_steps end reported as `truncated`
     (make_pipelines and the Gymnasium registration take them the same way)."""
     from .vector_env import WarehouseVecEnv
 

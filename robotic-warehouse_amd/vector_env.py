@@ -11,12 +11,17 @@ with obs float32 (B, N, L), rewards float32 (B, N), terminated/truncated bool (B
 step()'s info carries Gymnasium's "episode" / "_episode" keys on the steps that finish an episode.
 `action_mask=True` (opt-in): the step kernels write a valid-action byte per agent — `env.action_mask()`, bool (B, N, 5); with numpy
 output reset() and step() add info["action_mask"].
+`time_limit_truncates=True` (opt-in): an episode that ends by reaching `max_steps` sets `truncated`, only one that ends by
+`max_inactivity_steps` sets `terminated` (both when both rules fire on one step; `terminated | truncated` is the reference's `done` on
+every step) — what a learner that bootstraps from the value of the next state needs.  Autoreset, info["final_obs"] and info["episode"]
+follow `terminated | truncated`.  Off by default: the reference's behaviour, below.
 `obs_format="packed"` (opt-in, FLATTENED only): obs is uint32 (B, N, PW) instead — the same observation as bits, 16 bytes per agent
 at sensor_range 1 — and `env.unpack_obs(obs)` gives the float32 form back bit for bit (packing.py has the format).
 `obs_format="uint8"` (opt-in, IMAGE / IMAGE_DICT only): the image is uint8 (B, N, C, 2r+1, 2r+1) instead — the same values, 0 .. 4, one byte
 per element; `info["final_obs"]` and the IMAGE_DICT features stay float32.
 `obs[:, i, :]` is agent i's FLATTENED observation, i.e. element i of the reference's obs tuple
-(:944); `terminated` is the reference's `done` (:935-941); `truncated` is always False (:942).
+(:944); `terminated` is the reference's `done` (:935-941); `truncated` is always False (:942) unless
+`time_limit_truncates=True`.
 
 All simulation runs in the HIP engine (csrc/); this file only marshals arguments.  There is
 no CPU path: constructing the env without the built library or without a GPU raises.
@@ -164,7 +169,8 @@ class WarehouseVecEnv(_VectorEnvBase):
                  autoreset_mode: str = "next_step", devices=None, output: str = "numpy",
                  envs_per_workgroup: int = 0, threads_per_workgroup: int = 0, library: str | None = None,
                  obs_stores: str | None = None, jit=None, pipe=None, stats: bool = False, wave_priority=None,
-                 obs_format: str = "float32", episode_stats: bool = False, action_mask: bool = False):
+                 obs_format: str = "float32", episode_stats: bool = False, action_mask: bool = False,
+                 time_limit_truncates: bool = False):
         if obs_format not in ("float32", "packed", "uint8"):
             raise ValueError('obs_format must be "float32", "packed" or "uint8"')
         if not 0 <= int(msg_bits) <= 16:
@@ -276,7 +282,9 @@ class WarehouseVecEnv(_VectorEnvBase):
                 # True: the engine keeps per-episode return / length on the device (RW_EPISODES_ON) — see episode_stats()
                 episodes=episode_stats,
                 # True: the step kernels write the valid-action byte of every agent (RW_ACTION_MASK_ON) — see action_mask()
-                action_mask=action_mask))
+                action_mask=action_mask,
+                # True: a step-limit end sets `truncated`, only an inactivity end `terminated` (RW_TIME_LIMIT_TRUNCATES)
+                time_limit_truncates=time_limit_truncates))
         self._bounds = [b for b in self._bounds if b[1] > b[0]]
         self.shard_bounds = list(self._bounds)  # env range [lo, hi) of every engine / device, in order
         self.devices = devices[: len(self.engines)]
@@ -292,8 +300,10 @@ class WarehouseVecEnv(_VectorEnvBase):
         self._has_final_obs = autoreset_mode == "same_step"
         self._episode_stats = bool(episode_stats)
         self._action_mask = bool(action_mask)
+        self._time_limit_truncates = bool(time_limit_truncates)
         self._fast = None
-        self._fast_ok = output == "torch" and not self._dict_obs and len(devices) == 1
+        # (time_limit_truncates with same_step: info["_final_obs"] is terminated | truncated, one small torch kernel per step — step_wait)
+        self._fast_ok = output == "torch" and not self._dict_obs and len(devices) == 1 and not (self._time_limit_truncates and self._has_final_obs)
 
     # ------------------------------------------------------------------------------- spaces
     def _make_spaces(self):
@@ -442,7 +452,7 @@ class WarehouseVecEnv(_VectorEnvBase):
         """Warehouse.step (:804-946) for every env; actions (B, N) ints in 0..4 or Action members.
 
         With output="torch" all four results are zero-copy views of engine memory — the SAME tensor objects every call,
-        overwritten in place by the next step (obs, rewards, terminated; truncated stays False).  A loop that keeps them
+        overwritten in place by the next step (obs, rewards, terminated; truncated stays False unless time_limit_truncates).  A loop that keeps them
         across steps (`dones.append(terminated)`) must `.clone()` them; output="numpy" returns fresh host arrays."""
         fast = self._fast
         if fast is not None and type(actions) is fast[0] and actions.dtype is fast[1] and actions.is_contiguous() \
@@ -531,29 +541,35 @@ class WarehouseVecEnv(_VectorEnvBase):
             # the flag buffers are uint8 0/1: reinterpreted as bool, not cast (a cast is a torch kernel per flag per step
             # around a ~7 us step kernel)
             return self._observations(), v["rewards"], v["terminated_bool"], v["truncated_bool"], self._final_info(v)
-        # host arrays: the whole return tuple in one round trip per device (`truncated` is always False, :942 — nothing to read)
+        # host arrays: the whole return tuple in one round trip per device (`truncated` is always False, :942 — nothing to read — unless
+        # time_limit_truncates: then it comes along in the same round trip, rw_read_outputs2)
         if self._index_layers:
             self.sync()  # IndexError where the reference's _make_img_obs raises it
         want_f = self.observation_type == ObservationType.IMAGE_DICT
+        want_t = self._time_limit_truncates
         if len(self.engines) > 1:
             if self._pool is None:
                 from concurrent.futures import ThreadPoolExecutor
 
                 self._pool = ThreadPoolExecutor(len(self.engines))
-            parts = list(self._pool.map(lambda eng: eng.read_outputs(want_f), self.engines))
+            parts = list(self._pool.map(lambda eng: eng.read_outputs(want_f, want_t), self.engines))
             obs, rew, term = (np.concatenate([p[k] for p in parts], axis=0) for k in range(3))
             feat = np.concatenate([p[3] for p in parts], axis=0) if want_f else None
+            trunc = np.concatenate([p[4] for p in parts], axis=0) if want_t else None
         else:
-            obs, rew, term, feat = self.engines[0].read_outputs(want_f)
+            obs, rew, term, feat, *rest = self.engines[0].read_outputs(want_f, want_t)
+            trunc = rest[0] if want_t else None
+        trunc = trunc.view(np.bool_) if want_t else np.zeros(self.num_envs, np.bool_)
+        ended = (term | trunc.view(np.uint8)) if want_t else term  # the episode ended: the reference's `done`
         info = {}
-        if self._has_final_obs and term.any():  # (rare: the extra copy is made only on a step that ended an episode)
-            info = {"final_obs": self._gather("final_obs"), "_final_obs": term.view(np.bool_).copy()}
+        if self._has_final_obs and ended.any():  # (rare: the extra copy is made only on a step that ended an episode)
+            info = {"final_obs": self._gather("final_obs"), "_final_obs": ended.view(np.bool_).copy()}
             if self._dict_obs:
                 info["final_obs"] = self.dict_from_flat(info["final_obs"])
             elif want_f:  # IMAGE_DICT: the terminal observation is a dict like every other one (rware/warehouse.py:739-742)
                 info["final_obs"] = {"image": info["final_obs"], "features": self._gather("final_features")}
-        if self._episode_stats and term.any():  # Gymnasium's RecordEpisodeStatistics keys, on the steps that finish an episode only
-            done = term.view(np.bool_)
+        if self._episode_stats and ended.any():  # Gymnasium's RecordEpisodeStatistics keys, on the steps that finish an episode only
+            done = ended.view(np.bool_)
             info = dict(info, episode={"r": np.where(done[:, None], self._gather("ep_last_return"), np.float32(0)).astype(np.float32),
                                        "l": np.where(done, self._gather("ep_last_length"), 0).astype(np.int32)}, _episode=done.copy())
         if self._action_mask:  # the strict mask of the state `obs` describes
@@ -562,10 +578,11 @@ class WarehouseVecEnv(_VectorEnvBase):
             obs = self.dict_from_flat(obs)
         elif want_f:
             obs = {"image": obs, "features": feat}
-        return obs, rew, term.view(np.bool_), np.zeros(self.num_envs, np.bool_), info
+        return obs, rew, term.view(np.bool_), trunc, info
 
     def rollout(self, actions, want_obs=True):
-        """Open-loop rollout: `actions` (T, B, N) -> (obs (T,B,N,L), rewards (T,B,N), terminated (T,B)).
+        """Open-loop rollout: `actions` (T, B, N) -> (obs (T,B,N,L), rewards (T,B,N), terminated (T,B)) — with time_limit_truncates
+        a fourth element, truncated (T,B) bool (host and device tapes alike).
         One fused kernel launch per shard (`rw_step_many_device`): the env chunk stays in LDS across
         the T steps.  Bit-identical to T calls of step() with the same actions."""
         t = self._torch
@@ -581,7 +598,8 @@ class WarehouseVecEnv(_VectorEnvBase):
         a = a.reshape(a.shape[0], self.num_envs, self.n_agents * am)
         parts = [eng.rollout_host(a[:, lo:hi], want_obs) for eng, (lo, hi) in zip(self.engines, self._bounds)]
         cat = lambda k: parts[0][k] if len(parts) == 1 else np.concatenate([p[k] for p in parts], axis=1)
-        return (cat(0) if want_obs else None), cat(1), cat(2).astype(bool)
+        out = (cat(0) if want_obs else None), cat(1), cat(2).astype(bool)
+        return out + (cat(3).astype(bool),) if self._time_limit_truncates else out
 
     def _rollout_device(self, actions, want_obs):
         """rollout() with a CUDA action tape (T, B, N[, 1+M]) of an output="torch" env: the tapes come back as torch tensors
@@ -604,8 +622,10 @@ class WarehouseVecEnv(_VectorEnvBase):
         rew = t.empty((T, self.num_envs, self.n_agents), dtype=t.float32, device=dev)
         term = t.empty((T, self.num_envs), dtype=t.uint8, device=dev)
         self._live_actions = actions
-        eng.step_many_device(actions.data_ptr(), T, obs.data_ptr() if want_obs else 0, rew.data_ptr(), term.data_ptr())
-        return obs, rew, term.view(t.bool)
+        trunc = t.empty((T, self.num_envs), dtype=t.uint8, device=dev) if self._time_limit_truncates else None
+        eng.step_many_device(actions.data_ptr(), T, obs.data_ptr() if want_obs else 0, rew.data_ptr(), term.data_ptr(),
+                             trunc.data_ptr() if trunc is not None else 0)
+        return (obs, rew, term.view(t.bool)) + ((trunc.view(t.bool),) if trunc is not None else ())
 
     def capture_loop(self, policy, steps: int = 1, warmup: int = 2):
         """`steps` rounds of  `actions = policy(obs, rewards, terminated); env.step(actions)`  captured in ONE HIP graph.
@@ -618,6 +638,8 @@ class WarehouseVecEnv(_VectorEnvBase):
         (the usual case) is moved to a stream of its own for good (rw_set_stream) — replay() then orders that stream behind the
         caller's current stream and the caller's next ops behind the replay (two event waits per replay, no host sync), and
         eager env.step() calls keep working (they enqueue on the env's new stream: order them with `loop.stream` yourself).
+        With time_limit_truncates `policy` still gets `terminated`; the truncated flags are `envs.device_tensor("truncated")`, current on
+        every round of every replay.
         `policy` is called `warmup` times eagerly first (outputs discarded, the env does not step) so that lazy library
         initialisation happens outside the capture.
         `policy` may also reset: `envs.reset(seed=seed_tensor, mask=terminated)` with device tensors in front of computing its actions is
@@ -761,7 +783,9 @@ class WarehouseVecEnv(_VectorEnvBase):
     def _final_info(self, v, d=0):
         """SAME_STEP autoreset: the step that ends an episode returns the RESET observation; what the reference's step() returned
         with done = True (rware/warehouse.py:929-946) is kept as info["final_obs"], valid in the rows where info["_final_obs"]
-        (== terminated) is set — Gymnasium >= 1.0's vector-env convention.  Zero-copy views (torch output)."""
+        (== terminated) is set — Gymnasium >= 1.0's vector-env convention.  Zero-copy views (torch output).  With time_limit_truncates the
+        mask is terminated | truncated: ONE small torch kernel per step (bitwise_or) into a tensor allocated once — capturable, no
+        per-step allocation."""
         if not self._has_final_obs:
             return {}
         if "final_obs" not in v:
@@ -769,6 +793,12 @@ class WarehouseVecEnv(_VectorEnvBase):
             v["final_obs"] = t.as_tensor(eng.device_array("final_obs"), device=v["obs"].device)
             if self.observation_type == ObservationType.IMAGE_DICT:
                 v["final_obs"] = {"image": v["final_obs"], "features": t.as_tensor(eng.device_array("final_features"), device=v["obs"].device)}
+        if self._time_limit_truncates:
+            if "ended" not in v:
+                v["ended"] = t_ended = self._torch.empty_like(v["terminated"])
+                v["ended_bool"] = t_ended.view(self._torch.bool)
+            self._torch.bitwise_or(v["terminated"], v["truncated"], out=v["ended"])
+            return {"final_obs": v["final_obs"], "_final_obs": v["ended_bool"]}
         return {"final_obs": v["final_obs"], "_final_obs": v["terminated_bool"]}
 
     def _obs_of(self, v):
