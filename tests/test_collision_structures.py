@@ -158,12 +158,18 @@ def engine_run(task, z, idx, fused, who, library=None, **ctor):
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU
-def test_fixture_directory_stays_small():
-    files = glob.glob(os.path.join(FIX_DIR, "*.npz"))
-    assert sorted(os.path.basename(f)[:-4] for f in files) == sorted(TASKS)
-    golden = os.path.dirname(FIX_DIR)
+def check_fixture_directory_is_small(fix_dir, tasks):
+    """The size rule of a fixture directory under tests/golden/ (this one, and tests/golden/observations/): one .npz per task, under 2 MB
+    in all, none larger than the largest golden trace."""
+    files = glob.glob(os.path.join(fix_dir, "*.npz"))
+    assert sorted(os.path.basename(f)[:-4] for f in files) == sorted(tasks)
+    golden = os.path.dirname(fix_dir)
     largest_other = max(os.path.getsize(f) for f in glob.glob(os.path.join(golden, "*.npz")))
     assert sum(os.path.getsize(f) for f in files) < 2_000_000 and max(os.path.getsize(f) for f in files) <= largest_other
+
+
+def test_fixture_directory_stays_small():
+    check_fixture_directory_is_small(FIX_DIR, TASKS)
 
 
 @pytest.mark.parametrize("task", TASKS)
