@@ -59,6 +59,33 @@ RW_OBS_IMAGE_U8 = 8192  # rw_stream_flags: IMAGE / IMAGE_DICT observations as ui
 RW_TIME_LIMIT_TRUNCATES = 16384  # rw_stream_flags: reaching max_steps sets `truncated`, only max_inactivity_steps `terminated` (off by default: the reference's `terminated` = done)
 RW_STATS_ON = 128  # rw_stream_flags: keep the per-env event counters RW_BUF_STAT_DELIVERIES / _FAILED_MOVES (off by default)
 
+# rw_config.stream_flags, once: option name (the keyword of Engine / make_config) -> {accepted value: bits}.  A boolean option takes any
+# truth value; a tri-state one exactly the spellings listed (anything else is a KeyError); None / "auto" leave the choice to the engine.
+_switch = lambda bit: {False: 0, True: bit}
+_tri = lambda off, on, on_word: {None: 0, "auto": 0, False: off, "off": off, True: on, on_word: on}
+STREAM_FLAGS = {
+    "use_given_stream": _switch(RW_STREAM_USE_GIVEN),
+    "obs_stores": {None: 0, "auto": 0, "cached": RW_OBS_STORES_CACHED, "stream": RW_OBS_STORES_STREAM},
+    "jit": _tri(RW_JIT_OFF, RW_JIT_FORCE, "force"),
+    "pipe": _tri(RW_PIPE_OFF, RW_PIPE_ON, "on"),
+    "wave_priority": _tri(RW_PRIO_OFF, RW_PRIO_ON, "on"),
+    "stats": _switch(RW_STATS_ON), "obs_packed": _switch(RW_OBS_PACKED), "episodes": _switch(RW_EPISODES_ON),
+    "action_mask": _switch(RW_ACTION_MASK_ON), "obs_image_u8": _switch(RW_OBS_IMAGE_U8),
+    "time_limit_truncates": _switch(RW_TIME_LIMIT_TRUNCATES),
+}
+
+
+def stream_flags(**options) -> int:
+    """The rw_config.stream_flags word of these options (the names of STREAM_FLAGS; what is not given is off / the engine's choice)."""
+    word = 0
+    for name, value in options.items():
+        if name not in STREAM_FLAGS:
+            raise TypeError(f"stream_flags() got an unexpected option {name!r}")
+        table = STREAM_FLAGS[name]
+        word |= table[bool(value)] if table.keys() == {False, True} else table[value]
+    return word
+
+
 AUTORESET = {"disabled": 0, None: 0, "next_step": 1, "same_step": 2}
 
 
@@ -83,14 +110,96 @@ class RwInfo(C.Structure):
         ("pipe_workgroups", C.c_int32), ("stats", C.c_int32), ("obs_packed", C.c_int32)]
 
 
-EXPORTS = (
-    "rw_create", "rw_destroy", "rw_last_error", "rw_reset", "rw_step", "rw_step_device",
-    "rw_step_many_device", "rw_step_tape_device", "rw_step_tape_device_timed", "rw_refresh_obs", "rw_unpack_obs", "rw_refresh_grid", "rw_mark_views_stale", "rw_set_stream", "rw_jit_log", "rw_jit_probe", "rw_multi_create", "rw_multi_step_device", "rw_multi_destroy", "rw_sync", "rw_get_buffer", "rw_read", "rw_read_outputs", "rw_write",
-    "rw_recalc_grid", "rw_get_info", "rw_seed_state", "rw_event_record", "rw_event_elapsed_ms",
-    "rw_abi_version", "rw_debug_timeline", "rw_debug_store_floor", "rw_device_malloc", "rw_device_free", "rw_copy_to_device",
-    "rw_copy_to_host", "rw_selftest", "rw_snapshot_create", "rw_snapshot_save", "rw_snapshot_restore", "rw_snapshot_destroy",
-    "rw_seed_device", "rw_reset_device", "rw_global_image", "rw_step_many_device2", "rw_read_outputs2",
-)
+def make_config(*, abi_version=RW_ABI_VERSION, num_envs, layout, n_agents, sensor_range, request_queue_size, max_inactivity_steps, max_steps,
+                reward_type, normalised_coordinates=False, autoreset_mode="next_step", device_id=0, envs_per_workgroup=0,
+                threads_per_workgroup=0, stream=None, observation_type=1, image_layers=(), image_directional=True, msg_bits=0,
+                **flag_options) -> RwConfig:
+    """The rw_config of one engine, every field by name; `flag_options` are the options of STREAM_FLAGS.  The returned object keeps the
+    `highways` / `goals_xy` arrays it points at alive.  `abi_version`: a caller that drives another build of the library (an A/B
+    against a parent commit's) hands in that library's own rw_abi_version()."""
+    hw = np.ascontiguousarray(layout.highways, dtype=np.uint8)
+    goals = np.ascontiguousarray(np.asarray(layout.goals, dtype=np.int32).reshape(-1))
+    cfg = RwConfig(
+        abi_version=int(abi_version), num_envs=int(num_envs), grid_h=int(layout.grid_size[0]), grid_w=int(layout.grid_size[1]),
+        n_agents=int(n_agents), sensor_range=int(sensor_range), request_queue_size=int(request_queue_size),
+        max_inactivity_steps=int(max_inactivity_steps or 0), max_steps=int(max_steps or 0), reward_type=int(reward_type),
+        normalised_coordinates=int(bool(normalised_coordinates)), autoreset_mode=AUTORESET[autoreset_mode], n_goals=len(layout.goals),
+        device_id=int(device_id), envs_per_workgroup=int(envs_per_workgroup), threads_per_workgroup=int(threads_per_workgroup),
+        observation_type=int(observation_type), image_directional=int(bool(image_directional)), n_image_layers=len(image_layers),
+        image_layers=(C.c_int32 * 8)(*[int(l) for l in image_layers]), msg_bits=int(msg_bits), stream_flags=stream_flags(**flag_options),
+        highways=hw.ctypes.data, goals_xy=goals.ctypes.data, stream=C.c_void_p(stream or 0))
+    cfg._arrays = (hw, goals)
+    return cfg
+
+
+# Every entry point of include/rware_hip.h, once: name -> (restype, argtypes).  tests/test_capi_boundary.py compares the argument lists,
+# the two structures above and the flag values with the header.
+_vp, _i32, _sz, _str, _P = C.c_void_p, C.c_int32, C.c_size_t, C.c_char_p, C.POINTER
+PROTOTYPES = {
+    "rw_create": (C.c_int, (_P(RwConfig), _P(_vp))),
+    "rw_destroy": (C.c_int, (_vp,)),
+    "rw_last_error": (_str, (_vp,)),
+    "rw_reset": (C.c_int, (_vp, _vp, _vp)),
+    "rw_seed_device": (C.c_int, (_vp, _vp, _vp)),
+    "rw_reset_device": (C.c_int, (_vp, _vp, _vp)),
+    "rw_step": (C.c_int, (_vp, _vp)),
+    "rw_step_device": (C.c_int, (_vp, _vp)),
+    "rw_step_tape_device": (C.c_int, (_vp, _vp, _i32, _i32, _i32)),
+    "rw_step_tape_device_timed": (C.c_int, (_vp, _vp, _i32, _i32, _i32, _i32, _i32)),
+    "rw_step_many_device": (C.c_int, (_vp, _vp, _i32, _vp, _vp, _vp)),
+    "rw_step_many_device2": (C.c_int, (_vp, _vp, _i32, _vp, _vp, _vp, _vp)),
+    "rw_multi_create": (C.c_int, (_P(_vp), _i32, _P(_vp))),
+    "rw_multi_step_device": (C.c_int, (_vp, _P(_vp))),
+    "rw_multi_destroy": (C.c_int, (_vp,)),
+    "rw_device_malloc": (C.c_int, (_vp, _sz, _P(_vp))),
+    "rw_device_free": (C.c_int, (_vp, _vp)),
+    "rw_copy_to_device": (C.c_int, (_vp, _vp, _vp, _sz)),
+    "rw_copy_to_host": (C.c_int, (_vp, _vp, _vp, _sz)),
+    "rw_refresh_grid": (C.c_int, (_vp,)),
+    "rw_set_stream": (C.c_int, (_vp, _vp)),
+    "rw_mark_views_stale": (C.c_int, (_vp,)),
+    "rw_refresh_obs": (C.c_int, (_vp,)),
+    "rw_unpack_obs": (C.c_int, (_vp, _vp, _vp, C.c_int64)),
+    "rw_global_image": (C.c_int, (_vp, _P(_i32), _i32, _P(_i32), _i32, _vp)),
+    "rw_sync": (C.c_int, (_vp,)),
+    "rw_get_buffer": (C.c_int, (_vp, C.c_int, _P(_vp), _P(_sz))),
+    "rw_read": (C.c_int, (_vp, C.c_int, _vp, _sz)),
+    "rw_read_outputs": (C.c_int, (_vp, _vp, _vp, _vp, _vp)),
+    "rw_read_outputs2": (C.c_int, (_vp, _vp, _vp, _vp, _vp, _vp)),
+    "rw_write": (C.c_int, (_vp, C.c_int, _vp, _sz)),
+    "rw_recalc_grid": (C.c_int, (_vp, _vp, _i32)),
+    "rw_snapshot_create": (C.c_int, (_vp, _P(_vp))),
+    "rw_snapshot_save": (C.c_int, (_vp, _vp)),
+    "rw_snapshot_restore": (C.c_int, (_vp, _vp)),
+    "rw_snapshot_destroy": (C.c_int, (_vp, _vp)),
+    "rw_get_info": (C.c_int, (_vp, _P(RwInfo))),
+    "rw_jit_log": (_str, (_vp,)),
+    "rw_jit_probe": (C.c_int64, (_P(_i32), _str, _str, _sz)),
+    "rw_selftest": (C.c_int, (_i32, _str, _sz)),
+    "rw_seed_state": (C.c_int, (C.c_uint64, _vp)),
+    "rw_event_record": (C.c_int, (_vp, _i32)),
+    "rw_event_elapsed_ms": (C.c_int, (_vp, _i32, _i32, _P(C.c_float))),
+    "rw_debug_store_floor": (C.c_int, (_vp, _i32, _P(C.c_float))),
+    "rw_debug_timeline": (C.c_int, (_vp, _vp, _vp, _P(_i32), _P(_i32))),
+    "rw_abi_version": (C.c_int, ()),
+}
+EXPORTS = tuple(PROTOTYPES)
+
+
+def declare(lib, names=None):
+    """Applies PROTOTYPES (all of them, or `names`) to a CDLL and returns the names that library does not export — a parent commit's
+    library may be older than this description.  No ABI check: that is load()'s."""
+    missing = []
+    for name in PROTOTYPES if names is None else names:
+        restype, argtypes = PROTOTYPES[name]
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            missing.append(name)
+            continue
+        fn.restype, fn.argtypes = restype, list(argtypes)
+    return missing
+
 
 _libs = {}
 
@@ -128,59 +237,8 @@ def load(path: str | None = None):
             "g.build()'` (or `make -C robotic-warehouse_amd/csrc`). There is no CPU fallback.")
     _preload_hip_runtime()
     lib = C.CDLL(path)
-    vp, i32 = C.c_void_p, C.c_int32
-    lib.rw_create.argtypes = [C.POINTER(RwConfig), C.POINTER(vp)]
-    lib.rw_destroy.argtypes = [vp]
-    lib.rw_last_error.argtypes = [vp]
-    lib.rw_last_error.restype = C.c_char_p
-    lib.rw_reset.argtypes = [vp, vp, vp]
-    lib.rw_seed_device.argtypes = [vp, vp, vp]
-    lib.rw_reset_device.argtypes = [vp, vp, vp]
-    lib.rw_step.argtypes = [vp, vp]
-    lib.rw_step_device.argtypes = [vp, vp]
-    lib.rw_step_many_device.argtypes = [vp, vp, i32, vp, vp, vp]
-    lib.rw_step_many_device2.argtypes = [vp, vp, i32, vp, vp, vp, vp]
-    lib.rw_step_tape_device.argtypes = [vp, vp, i32, i32, i32]
-    lib.rw_step_tape_device_timed.argtypes = [vp, vp, i32, i32, i32, i32, i32]
-    lib.rw_refresh_obs.argtypes = [vp]
-    lib.rw_unpack_obs.argtypes = [vp, vp, vp, C.c_int64]
-    lib.rw_global_image.argtypes = [vp, C.POINTER(i32), i32, C.POINTER(i32), i32, vp]
-    lib.rw_refresh_grid.argtypes = [vp]
-    lib.rw_mark_views_stale.argtypes = [vp]
-    lib.rw_set_stream.argtypes = [vp, vp]
-    lib.rw_jit_log.argtypes = [vp]
-    lib.rw_jit_log.restype = C.c_char_p
-    lib.rw_jit_probe.argtypes = [C.POINTER(C.c_int32), C.c_char_p, C.c_char_p, C.c_size_t]
-    lib.rw_jit_probe.restype = C.c_int64
-    lib.rw_selftest.argtypes = [i32, C.c_char_p, C.c_size_t]
-    lib.rw_debug_store_floor.argtypes = [vp, i32, C.POINTER(C.c_float)]
-    lib.rw_multi_create.argtypes = [C.POINTER(vp), i32, C.POINTER(vp)]
-    lib.rw_multi_step_device.argtypes = [vp, C.POINTER(vp)]
-    lib.rw_multi_destroy.argtypes = [vp]
-    lib.rw_sync.argtypes = [vp]
-    lib.rw_get_buffer.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    lib.rw_read.argtypes = [vp, C.c_int, vp, C.c_size_t]
-    lib.rw_read_outputs.argtypes = [vp, vp, vp, vp, vp]
-    lib.rw_read_outputs2.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.rw_write.argtypes = [vp, C.c_int, vp, C.c_size_t]
-    lib.rw_recalc_grid.argtypes = [vp, vp, i32]
-    lib.rw_get_info.argtypes = [vp, C.POINTER(RwInfo)]
-    lib.rw_seed_state.argtypes = [C.c_uint64, vp]
-    lib.rw_event_record.argtypes = [vp, i32]
-    lib.rw_event_elapsed_ms.argtypes = [vp, i32, i32, C.POINTER(C.c_float)]
-    lib.rw_abi_version.argtypes = []
-    lib.rw_debug_timeline.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
-    lib.rw_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
-    lib.rw_device_free.argtypes = [vp, vp]
-    lib.rw_copy_to_device.argtypes = [vp, vp, vp, C.c_size_t]
-    lib.rw_copy_to_host.argtypes = [vp, vp, vp, C.c_size_t]
-    lib.rw_snapshot_create.argtypes = [vp, C.POINTER(vp)]
-    lib.rw_snapshot_save.argtypes = [vp, vp]
-    lib.rw_snapshot_restore.argtypes = [vp, vp]
-    lib.rw_snapshot_destroy.argtypes = [vp, vp]
-    for name in EXPORTS:
-        if name not in ("rw_last_error", "rw_jit_log", "rw_jit_probe"):
-            getattr(lib, name).restype = C.c_int
+    for name in declare(lib):  # (this tree's own library has every entry point: what ctypes itself says of a missing one)
+        raise AttributeError(f"{path}: undefined symbol: {name}")
     if lib.rw_abi_version() != RW_ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.rw_abi_version()} != {RW_ABI_VERSION}")
     _libs[path] = lib
@@ -224,23 +282,15 @@ class Engine:
         self.lib = load(library)
         self._h = C.c_void_p()
         self._arena, self.arena_allocations = {}, 0  # rollout_host's device tapes (grow-only; freed in close())
-        hw = np.ascontiguousarray(layout.highways, dtype=np.uint8)
-        goals = np.ascontiguousarray(np.asarray(layout.goals, dtype=np.int32).reshape(-1))
-        cfg = RwConfig(
-            RW_ABI_VERSION, int(num_envs), int(layout.grid_size[0]), int(layout.grid_size[1]), int(n_agents),
-            int(sensor_range), int(request_queue_size), int(max_inactivity_steps or 0), int(max_steps or 0),
-            int(reward_type), int(bool(normalised_coordinates)), AUTORESET[autoreset_mode], len(layout.goals),
-            int(device_id), int(envs_per_workgroup), int(threads_per_workgroup),
-            int(observation_type), int(bool(image_directional)), len(image_layers),
-            (C.c_int32 * 8)(*[int(l) for l in image_layers]), int(msg_bits),
-            (RW_STREAM_USE_GIVEN if use_given_stream else 0) | {None: 0, "auto": 0, "cached": RW_OBS_STORES_CACHED, "stream": RW_OBS_STORES_STREAM}[obs_stores]
-            | {None: 0, "auto": 0, False: RW_JIT_OFF, "off": RW_JIT_OFF, True: RW_JIT_FORCE, "force": RW_JIT_FORCE}[jit]
-            | {None: 0, "auto": 0, False: RW_PIPE_OFF, "off": RW_PIPE_OFF, True: RW_PIPE_ON, "on": RW_PIPE_ON}[pipe]
-            | (RW_STATS_ON if stats else 0) | (RW_OBS_PACKED if obs_packed else 0) | (RW_EPISODES_ON if episodes else 0)
-            | (RW_ACTION_MASK_ON if action_mask else 0) | (RW_OBS_IMAGE_U8 if obs_image_u8 else 0)
-            | (RW_TIME_LIMIT_TRUNCATES if time_limit_truncates else 0)
-            | {None: 0, "auto": 0, False: RW_PRIO_OFF, "off": RW_PRIO_OFF, True: RW_PRIO_ON, "on": RW_PRIO_ON}[wave_priority],
-            hw.ctypes.data, goals.ctypes.data, C.c_void_p(stream or 0))
+        cfg = make_config(
+            num_envs=num_envs, layout=layout, n_agents=n_agents, sensor_range=sensor_range, request_queue_size=request_queue_size,
+            max_inactivity_steps=max_inactivity_steps, max_steps=max_steps, reward_type=reward_type,
+            normalised_coordinates=normalised_coordinates, autoreset_mode=autoreset_mode, device_id=device_id,
+            envs_per_workgroup=envs_per_workgroup, threads_per_workgroup=threads_per_workgroup, stream=stream,
+            observation_type=observation_type, image_layers=image_layers, image_directional=image_directional, msg_bits=msg_bits,
+            use_given_stream=use_given_stream, obs_stores=obs_stores, jit=jit, pipe=pipe, stats=stats, wave_priority=wave_priority,
+            obs_packed=obs_packed, episodes=episodes, action_mask=action_mask, obs_image_u8=obs_image_u8,
+            time_limit_truncates=time_limit_truncates)
         rc = self.lib.rw_create(C.byref(cfg), C.byref(self._h))
         if rc != RW_OK:
             raise EngineError(rc, (self.lib.rw_last_error(None) or b"").decode())
