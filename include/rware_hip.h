@@ -45,7 +45,11 @@ extern "C" {
  * caller's, enqueue only); no struct, flag or buffer kind changes (RW_BUF_KIND_COUNT stays 29).
  * Still 4, a compatible addition: RW_TIME_LIMIT_TRUNCATES in rw_stream_flags (RW_BUF_TRUNCATED becomes live with it; no new buffer kind,
  * RW_BUF_KIND_COUNT stays 29), bit 3 of rw_info.stats, and two entry points, rw_step_many_device2 and rw_read_outputs2 (their namesakes
- * plus the truncated flags); rw_info keeps its size, rw_step_many_device and rw_read_outputs are unchanged. */
+ * plus the truncated flags); rw_info keeps its size, rw_step_many_device and rw_read_outputs are unchanged.
+ * Still 4, a compatible addition: rw_config.n_agents takes 1..127 (was 1..64).  65 .. 127 agents always run the generic kernel
+ * (rw_info.build_kind 0, no run-time build, not even with RW_JIT_FORCE; rw_jit_log says so), by default on workgroups of 4 envs, and
+ * envs_per_workgroup * n_agents must stay below 2355 there.  128 and more stay RW_ERR_INVALID_ARG: the kernels' per-cell agent layer
+ * holds id | 0x80 (loaded) in one byte.  No struct, flag, buffer kind or entry point changes. */
 #define RW_ABI_VERSION 4
 
 typedef struct rw_engine rw_engine;
@@ -315,7 +319,7 @@ typedef struct rw_config {
     int32_t abi_version;          /* RW_ABI_VERSION                                              */
     int32_t num_envs;             /* B                                                           */
     int32_t grid_h, grid_w;       /* grid_size (:297-300)                                        */
-    int32_t n_agents;             /* N, 1..64                                                    */
+    int32_t n_agents;             /* N, 1..127 (more than 64: the generic kernel only)           */
     int32_t sensor_range;         /* r, 1..5 ; L = 8 + 7*(2r+1)^2 (:432-443, msg_bits == 0)      */
     int32_t request_queue_size;   /* Q                                                           */
     int32_t max_inactivity_steps; /* 0 == None                                                   */

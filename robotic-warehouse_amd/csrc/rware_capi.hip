@@ -616,8 +616,11 @@ int check_config(const rw_config *cfg, Shape *out) {
     if (cfg->abi_version != RW_ABI_VERSION)
         return fail(nullptr, RW_ERR_INVALID_ARG, "abi_version %d != %d", cfg->abi_version, RW_ABI_VERSION);
     const int B = cfg->num_envs, H = cfg->grid_h, W = cfg->grid_w, N = cfg->n_agents, Q = cfg->request_queue_size;
-    if (B < 1 || H < 1 || W < 1 || N < 1 || N > 64 || Q < 0 || !cfg->highways || !cfg->goals_xy || cfg->n_goals < 1)
+    if (B < 1 || H < 1 || W < 1 || N < 1 || Q < 0 || !cfg->highways || !cfg->goals_xy || cfg->n_goals < 1)
         return fail(nullptr, RW_ERR_INVALID_ARG, "bad shape: B=%d H=%d W=%d N=%d Q=%d n_goals=%d", B, H, W, N, Q, cfg->n_goals);
+    if (N > 127)  // (the kernels' per-cell agent layer is one byte: agent id 1 .. 127, bit 7 the loaded flag)
+        return fail(nullptr, RW_ERR_INVALID_ARG, "n_agents %d not in 1..127: the agent layer holds id | 0x80 (loaded) in one byte per cell, "
+                    "128 agents would need a wider layer", N);
     if (cfg->sensor_range < 1 || cfg->sensor_range > 5)
         return fail(nullptr, RW_ERR_UNSUPPORTED, "sensor_range %d not in 1..5", cfg->sensor_range);
     if (cfg->reward_type < 0 || cfg->reward_type > 2 || cfg->autoreset_mode < 0 || cfg->autoreset_mode > 2)
@@ -880,8 +883,14 @@ int pick_build(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *b) {
         E = (int)((32 * 1024) / per_env) & ~3;
         if (E < 4) E = 4;
         if (E > 16) E = 16;  // measured best on MI355X for the registered configs (profiles/)
+        if (s.N > 64) E = 4;  // (an env's agent phases take a whole wavefront there: one env per wavefront of the 256 threads)
     }
     if (E % 4 || E < 4) return fail(eng, RW_ERR_INVALID_ARG, "envs_per_workgroup %d must be a positive multiple of 4", E);
+    // more than 64 agents: rw_div18(i, magic18(N)) == i / N for every i < E * N only below i = 2355 (the first wrong quotient of an
+    // exhaustive scan over N = 65 .. 127: 2355 / 124) — the bound below is a sufficient one in N alone and does not reach that far up
+    if (s.N > 64 && (long long)E * s.N >= 2355)
+        return fail(eng, RW_ERR_INVALID_ARG, "envs_per_workgroup %d too large for N=%d: with more than 64 agents a workgroup holds fewer than "
+                    "2355 agents (the kernels divide by N with an 18-bit reciprocal)", E, s.N);
     // x / N == (x * ceil(2^18 / N)) >> 18 needs x * N < 2^18 for every x < E * N
     if ((long long)E * s.N * s.N >= (1 << 18))
         return fail(eng, RW_ERR_INVALID_ARG, "envs_per_workgroup %d too large for N=%d Q=%d", E, s.N, s.Q);
@@ -898,6 +907,10 @@ int pick_build(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *b) {
     b->rollout = pick(true, s.wide, s.image, s.M > 0);
     b->E = E;
     b->T = T;
+    if (s.N > 64) {  // only the generic kernels hold the two-agents-per-lane agent phases (rware_phase_agents_wide.h): no table entry, no run-time build
+        jit_note(eng, "more than 64 agents: the generic kernel");
+        return RW_OK;
+    }
     if (!(s.image && s.M > 0)) pick_static(eng, cfg, s, b);  // (image + messages together: generic builds only)
     return RW_OK;
 }
@@ -913,6 +926,7 @@ void try_jit_build(rw_engine *eng, const rw_config *cfg, const Shape &s, Build *
     // (image + messages together: no float32 engine has had a specialised build, ahead of time or at run time; the uint8 images get theirs —
     //  every image shape of an RW_OBS_IMAGE_U8 engine has a run-time build, kObs == OBS_IMAGE_MSG with the message bits baked in)
     const bool combo_ok = !(s.image && s.M > 0) || (eng->features & F_IMAGE_U8) != 0;
+    if (s.N > 64) return;  // (not even with RW_JIT_FORCE: pick_build has said why in the log)
     if (!combo_ok || !(mode == 1 || (mode == 0 && !aot_exact && s.B >= 4096))) return;
     const bool geom_given = cfg->envs_per_workgroup != 0 || cfg->threads_per_workgroup != 0;
     const int N = s.N, B = s.B;

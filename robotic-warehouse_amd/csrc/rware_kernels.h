@@ -148,7 +148,7 @@ struct Params {
     int32_t n_goals, max_inactivity, max_steps, reward_type, autoreset, normalised;
     int32_t envs_per_wg;
     int32_t nt_obs;                    // 1: the observation stream is stored with the non-temporal hint (see ST)
-    int32_t groups_per_wave;           // envs whose agents share one wavefront = 64 / N
+    int32_t groups_per_wave;           // envs whose agents share one wavefront = 64 / N (more than 64 agents: 0, and the agent phases do not read it)
     uint32_t magic_n;                  // ceil(2^18 / N): x / N == (x * magic) >> 18 for x * N < 2^18
     int32_t goal_cells[MAX_GOALS];     // cell index y*W+x per goal, list order
     const int32_t *shelf_init;     // [HW] shelf layer right after reset: ids 1..S row-major on non-highway cells
@@ -775,11 +775,22 @@ rware_step_kernel(const Params *__restrict__ cp, RW_LAUNCH_PARAMS) {
     //           With kDirect the own record does not come from LDS either: the lane fetched it from HBM into registers
     //           at the top of the kernel.
     //   else    the sub-phases exchange through LDS arrays under wave_sync() (any N up to 64, run-time shapes).
+    //   wide    65 .. 127 agents, generic kernels: the same LDS exchange, one env per wavefront, two agents per lane.
     if constexpr (kPipe) { if (pipe_wave == 0) load_own_lds(); }
     if constexpr (kRegAG) {
 #include "rware_phase_agents_reg.h"
     } else {
+        // (the generic kernels — every shape at run time — also serve 65 .. 127 agents: an env then takes a whole wavefront, two agents
+        //  per lane.  The branch is wave-uniform and exists in those kernels only: no exact-shape, size-static or run-time build sees it)
+        if constexpr (Cfg::kN == 0 && Cfg::kE == 0) {
+            if (RW_RARE(N > 64)) {
+#include "rware_phase_agents_wide.h"
+            } else {
 #include "rware_phase_agents_lds.h"
+            }
+        } else {
+#include "rware_phase_agents_lds.h"
+        }
     }
     RW_PIPE_MARK_PREV(4, 0, TL_PIPE_FIRST_AG);  // (the agent phases of this chunk ran one stage ago: slot 4 of chunk it - 1)
     lds_barrier();  // (PIPE: barrier A)
