@@ -47,6 +47,8 @@ def kwargs_of(task):
 
 
 def name_of(task, z, k, t):
+    if "describe" in z:     # (a fixture of another directory names its scenarios itself: tests/test_shelf_handling.py)
+        return z["describe"](task, k, t)
     return (f"{task}, scenario {k} ({cs.FAMILIES[z['family'][k]]} / {z['variant'][k]}, claims {z['claim'][k]}), "
             f"ids {cs.ID_ASSIGNMENTS[z['ids'][k]]}, step {t}")
 
@@ -63,7 +65,8 @@ def inject(be, z, idx, seed_reset=True):
     B = len(idx)
     fields = {f: z[f][idx].astype(np.int32) for f in AGENT_FIELDS}
     fields["queue"] = z["queue"][idx].astype(np.int32)
-    fields["rng"] = np.repeat(z["rng0"][None], B, axis=0)
+    fields["rng"] = z["rng"][idx] if "rng" in z else np.repeat(z["rng0"][None], B, axis=0)     # (one state per scenario, or the reset's)
+    fields.update({f: z[f][idx].astype(np.int32) for f in ("steps", "inactive") if f in z})
     sxy = np.ascontiguousarray(z["shelf_xy"][idx].astype(np.int32))
     if isinstance(be, OracleVecEnv):
         be.reset(seed=z["meta"]["seed"])
@@ -97,6 +100,10 @@ def check_state(task, z, idx, t, state, shelf_xy, rew=None, done=None, who=""):
     if not np.array_equal(np.asarray(state["queue"]), z["r_queue"][idx, t]):
         e = int(np.argwhere((np.asarray(state["queue"]) != z["r_queue"][idx, t]).any(-1))[0, 0])
         fail(e, f"queue {np.asarray(state['queue'])[e].tolist()}, reference {z['r_queue'][idx, t][e].tolist()}")
+    for f in ("steps", "inactive", "rng") if "r_steps" in z else ():     # (the fixtures that record the counters: tests/golden/handling)
+        if not np.array_equal(np.asarray(state[f]), z["r_" + f][idx, t]):
+            e = int(np.argwhere((np.asarray(state[f]) != z["r_" + f][idx, t]).reshape(len(idx), -1).any(-1))[0, 0])
+            fail(e, f"{f} {np.asarray(state[f])[e].tolist()}, reference {z['r_' + f][idx, t][e].tolist()}")
     if rew is not None:
         got, want = np.round(np.asarray(rew, np.float64) * 2).astype(np.int64), z["r_rewards_x2"][idx, t]
         if not np.array_equal(got, want):
@@ -115,24 +122,25 @@ def check_same(task, z, idx, t, what, got, want, who=""):
         raise AssertionError(f"{who}{name_of(task, z, int(idx[e]), t)}: {what} of agent {i} differs from the oracle's")
 
 
-def oracle_run(task, z, idx):
+def oracle_run(task, z, idx, kwargs=None):
     """The oracle on the injected batch: [(obs, rewards, done)] per step, checked against the fixture on the way."""
-    orc = OracleVecEnv(len(idx), **kwargs_of(task))
+    orc = OracleVecEnv(len(idx), **(kwargs or kwargs_of(task)))
     out = [inject(orc, z, idx)]
-    for t in range(T):
+    for t in range(z["meta"]["steps"]):
         rew, done = orc.step(z["actions"][idx, t].astype(np.int32))
         check_state(task, z, idx, t, orc.get_state(), orc.shelf_xy(), rew, done, who="oracle: ")
         out.append((orc.obs(), rew, done))
     return out
 
 
-def engine_run(task, z, idx, fused, who, library=None, **ctor):
+def engine_run(task, z, idx, fused, who, library=None, kwargs=None, **ctor):
     """The engine on the injected batch against fixture (every field, every step) and oracle (observations, rewards, done).
     A fused rollout hands back no state between its steps: there the fixture's rewards and done are compared at every step through
     the oracle (itself checked against the fixture at every step, just above), observations against the oracle's at every step,
     and the state against the fixture behind the last step."""
-    ora = oracle_run(task, z, idx)
-    env = rware_amd.WarehouseVecEnv(len(idx), autoreset_mode="disabled", library=library, **kwargs_of(task), **ctor)
+    ora = oracle_run(task, z, idx, kwargs)
+    env = rware_amd.WarehouseVecEnv(len(idx), autoreset_mode="disabled", library=library, **(kwargs or kwargs_of(task)), **ctor)
+    T = z["meta"]["steps"]
     try:
         unpack = env.unpack_obs if ctor.get("obs_format") == "packed" else (lambda o: o)
         check_same(task, z, idx, 0, "the observation of the injected state", unpack(inject(env, z, idx)), ora[0], who)
