@@ -31,6 +31,12 @@ FAMILIES = ("chain", "blocked_head", "cycle", "swap", "junction", "head_loses", 
 ID_ASSIGNMENTS = ("ascending", "descending", "random", "boundary")
 
 
+def name_of(task, z, k, t):
+    """Scenario k of a recorded fixture of these scenarios (tests/golden/collisions, tests/golden/wide/collisions-straddle) at step t."""
+    return (f"{task}, scenario {k} ({FAMILIES[z['family'][k]]} / {z['variant'][k]}, claims {z['claim'][k]}), "
+            f"ids {ID_ASSIGNMENTS[z['ids'][k]]}, step {t}")
+
+
 # ------------------------------------------------------------------------------------------------------------------ census
 def analyse(ax, ay, ad, ac, actions, H, W, shelf_layer):
     """(Counter of classes, set of agents that change cell this step) for one env.  `shelf_layer`: (H, W) shelf ids at the START

@@ -12,6 +12,12 @@ from rware_oracle import OracleVecEnv
 P_DEFAULT = [.1, .55, .1, .1, .15]
 
 
+def default_envs_per_workgroup(task, N):
+    # the table's rule for small batches (csrc/rware_static_table.h): 16 envs up to 4 agents, 8 from 5 on; 9 .. 19 agents on the small
+    # warehouse step on 4-env workgroups below one round of them and roll out on 8 (13 .. 16 agents), the tiny one has 8-env builds only
+    return 16 if N <= 4 else 4 if task.startswith("small") and N >= 9 else 8
+
+
 def square(max_steps):
     """A 10 x 10 grid: the transposed index of the AGENT_DIRECTION / AGENT_LOAD layers is always in bounds."""
     return dict(shelf_columns=3, column_height=3, shelf_rows=2, n_agents=5, msg_bits=0, sensor_range=2,

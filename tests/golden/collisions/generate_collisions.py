@@ -20,6 +20,7 @@ for p in (os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 import collision_scenarios as cs  # noqa: E402
+import pins  # noqa: E402
 import ref_runner as rr  # noqa: E402
 
 SEED = 2024          # reset seed of every task
@@ -29,24 +30,6 @@ TASKS = {f"tiny-{n}ag": (f"rware-tiny-{n}ag-v2", cap) for n, cap in
          [(2, 400), (3, 400), (4, 600), (5, 600), (6, 900), (7, 900), (8, 900), (9, 1200), (12, 1200), (13, 1200), (16, 1200), (17, 1200), (19, 1200)]}
 TASKS["small-4ag"] = ("rware-small-4ag-v2", 600)
 TASKS["small-16ag"] = ("rware-small-16ag-v2", 1200)
-
-
-def inject(env, sc, rng_state=None):
-    """One scenario (agent_x / agent_y / agent_dir / agent_carry (N,), shelf_xy (S, 2), queue (Q,)) into a reference env, the way the
-    reference's own tests do it: overwrite the objects, zero the counters, `_recalc_grid()`."""
-    wh = rr.load_reference()
-    for i, ag in enumerate(env.agents):
-        ag.x, ag.y, ag.dir = int(sc["agent_x"][i]), int(sc["agent_y"][i]), wh.Direction(int(sc["agent_dir"][i]))
-        c = int(sc["agent_carry"][i])
-        ag.carrying_shelf = env.shelfs[c - 1] if c else None
-        ag.has_delivered = False
-    for s, (x, y) in zip(env.shelfs, sc["shelf_xy"]):
-        s.x, s.y = int(x), int(y)
-    env.request_queue = [env.shelfs[int(q) - 1] for q in sc["queue"]]
-    env._cur_steps = env._cur_inactive_steps = 0
-    if rng_state is not None:
-        env.np_random.bit_generator.state = rng_state
-    env._recalc_grid()
 
 
 def record_task(name, out_dir=HERE):
@@ -69,7 +52,7 @@ def record_task(name, out_dir=HERE):
                r_req_action=np.zeros((n, cs.T_STEPS, N), np.int16))
     classes = {}
     for k, sc in enumerate(scen):
-        inject(env, sc, rng_state)
+        pins.inject_reference(env, sc, rng_state)
         cen = cs.census(sc, sc["actions"][0], H, W, cs.shelf_layer_from_xy(sc["shelf_xy"], H, W))
         for c, v in cen.items():
             classes[c] = classes.get(c, 0) + v

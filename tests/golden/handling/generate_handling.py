@@ -3,7 +3,7 @@ tests/handling_scenarios.py.  Run:  python tests/golden/handling/generate_handli
 
 Per task and configuration of handling_scenarios.CONFIGS (the three reward types with `max_steps` / `max_inactivity_steps` set to
 handling_scenarios.LIMITS, and TWO_STAGE with no limit) one reference `Warehouse` is reset once (seed in `meta`).  Every scenario
-overwrites its objects the way the reference's own tests do — the injector of the collision fixtures, plus `has_delivered`, `_cur_steps`,
+overwrites its objects the way the reference's own tests do — pins.inject_reference with `has_delivered`, `_cur_steps`,
 `_cur_inactive_steps` and the PCG64 state — and takes T_STEPS steps under the pinned tie-break of oracle/ref_runner.py.
 
 Stored per scenario: the injected state and the T x N actions; after every step the agents' x / y / dir / carry, every shelf's (x, y),
@@ -15,7 +15,6 @@ the FLATTENED rows of the injected state and of every step are stored bit-packed
 The generator refuses to write a task in which a family that its geometry admits yields no scenario, a scenario's census misses its claim,
 or a class that the geometry admits is held by no scenario.
 """
-import importlib.util
 import json
 import os
 import sys
@@ -29,6 +28,7 @@ for p in (os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 import handling_scenarios as hs  # noqa: E402
+import pins  # noqa: E402
 import ref_runner as rr  # noqa: E402
 import rng_states as rs  # noqa: E402
 import wide_fixtures as wf  # noqa: E402
@@ -49,24 +49,6 @@ TASKS.update({
     "tiny-65ag": (None, dict(_CUSTOM, shelf_columns=3, column_height=8, shelf_rows=1, n_agents=65, request_queue_size=20)),    # no oracle: observations stored
 })
 AGENT_FIELDS = ("agent_x", "agent_y", "agent_dir", "agent_carry")
-
-
-def _load_collisions():
-    spec = importlib.util.spec_from_file_location("generate_collisions", os.path.join(os.path.dirname(HERE), "collisions", "generate_collisions.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-_collisions = _load_collisions()     # (once: inject runs per scenario and configuration)
-
-
-def inject(env, sc):
-    """generate_collisions.inject, then the fields it zeroes: the flags, the two counters and the generator state."""
-    _collisions.inject(env, sc, rs.numpy_state(sc["rng"]))
-    for ag, f in zip(env.agents, sc["agent_delivered"]):
-        ag.has_delivered = bool(f)
-    env._cur_steps, env._cur_inactive_steps = int(sc["steps"]), int(sc["inactive"])
 
 
 def reference_env(name, c):
@@ -117,7 +99,7 @@ def record_task(name, out_dir=HERE):
     census = [Counter() for _ in range(C)]
     for k, sc in enumerate(scen):
         for c, env in enumerate(envs):
-            inject(env, sc)
+            pins.inject_reference(env, sc, rs.numpy_state(sc["rng"]), counters=True)
             sh = hs.config_shape(shape, c)
             before, by_step = state_of(env), []
             if wide and c == 0:

@@ -2,7 +2,7 @@
 constructed observation scenarios of tests/observation_scenarios.py.  Run:  python tests/golden/observations/generate_observations.py
 
 Per task one reference `Warehouse` is reset once (seed in `meta`); every scenario is injected the way
-tests/golden/collisions/generate_collisions.py does it (objects overwritten, counters 0, the PCG64 state of the reset,
+tests/pins.inject_reference does it (objects overwritten, counters 0, the PCG64 state of the reset,
 `_recalc_grid()`; messages cleared), then:
 
   observation 0    `_make_obs` of every agent on the injected state
@@ -17,7 +17,6 @@ over the last axis); the two coordinates of a FLATTENED row stay float32.  A sce
 `meta` holds the census of the injected states (tests/observation_scenarios.window_census), the family counts and the random-play
 floor: how many census classes random play (`floor_play` envs x steps) reaches on the C oracle, beside how many the fixture holds.
 """
-import importlib.util
 import json
 import os
 import sys
@@ -31,6 +30,7 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 import observation_scenarios as osc  # noqa: E402
+import pins  # noqa: E402
 import ref_runner as rr  # noqa: E402
 
 SEED = 2025          # reset seed of every task
@@ -111,13 +111,6 @@ for _n in LAYOUTS:
     TASKS[f"img-layout-{_n}"] = (None, _layout_kwargs(_n, True))
 
 
-def _collisions():
-    spec = importlib.util.spec_from_file_location("generate_collisions", os.path.join(os.path.dirname(HERE), "collisions", "generate_collisions.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def reference_env(env_id, extra):
     wh = rr.load_reference()
     kw = rr.registry_kwargs(env_id) if env_id else {}
@@ -139,9 +132,9 @@ def shape_of(env, goals_family=False):
 
 
 def inject(env, sc, rng_state):
-    """generate_collisions.inject, plus what it has no need for: messages cleared, the scenario's reward type."""
+    """pins.inject_reference, plus what the other pins have no need for: messages cleared, the scenario's reward type."""
     wh = rr.load_reference()
-    _collisions().inject(env, sc, rng_state)
+    pins.inject_reference(env, sc, rng_state)
     for ag in env.agents:
         ag.message[:] = 0
     if sc.get("reward_type") is not None:

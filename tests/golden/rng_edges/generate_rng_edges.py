@@ -5,13 +5,12 @@ The task ids of rng_states.TASKS end in -v2: that is what the reference register
 Per task (rng_states.TASKS) one reference `Warehouse` is reset once (seed in `meta`).
   Reset scenarios (rs_*): the constructed state goes into `env.np_random`, then `reset()` with no seed.  Stored: the state before
   (rs_rng0), and after it agent_x / agent_y / agent_dir, the queue and the six state words (rs_r_*).
-  Delivery scenarios (dl_*): requested shelves are put onto goal cells by the injector of the collision fixtures (objects overwritten,
+  Delivery scenarios (dl_*): requested shelves are put onto goal cells by tests/pins.inject_reference (objects overwritten,
   `_recalc_grid()`), the constructed state goes into `env.np_random`, one all-NOOP step follows.  Stored: the injected state (agents,
   every shelf's (x, y), queue, state words) and after the step the queue, rewards (x 2, so TWO_STAGE halves stay integers), done,
   agent_delivered and the state words (dl_r_*).
 `meta` holds the scenario names, the claim of each and the counts; no observations (they are compared engine <-> oracle).
 """
-import importlib.util
 import json
 import os
 import sys
@@ -23,17 +22,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(HERE)))
 for p in (os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
+import pins  # noqa: E402
 import ref_runner as rr  # noqa: E402
 import rng_states as rs  # noqa: E402
 
 SEED = 2025          # reset seed of every task; its increment is the one every constructed state of the task carries
-
-
-def _collision_injector():
-    spec = importlib.util.spec_from_file_location("generate_collisions", os.path.join(os.path.dirname(HERE), "collisions", "generate_collisions.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.inject
 
 
 def delivery_state(sc, H, W, N, highways, goals):
@@ -64,7 +57,6 @@ def record_task(name, out_dir=HERE):
         kw["reward_type"] = wh.RewardType(kw["reward_type"])
     env = rr.make_reference_env(env_id, **kw)
     env.reset(seed=SEED)
-    inject = _collision_injector()
     H, W = env.grid_size
     N, S, Q = env.n_agents, len(env.shelfs), env.request_queue_size
     goals = [(int(x), int(y)) for x, y in env.goals]
@@ -96,7 +88,7 @@ def record_task(name, out_dir=HERE):
         rec["dl_" + f] = np.stack([st[f] for st in states]).astype(dt)
     for k, (sc, st) in enumerate(zip(deliveries, states)):
         env.reset(seed=SEED)        # (fresh Shelf / Agent objects: a delivery scenario starts from the same env every time)
-        inject(env, st, rs.numpy_state(sc.state))
+        pins.inject_reference(env, st, rs.numpy_state(sc.state))
         _, rew, done, _, _ = rr.ref_step(env, [0] * N)
         snap = rr.snapshot(env)
         rec["dl_r_queue"][k], rec["dl_r_rng"][k] = snap["queue"], snap["rng"]

@@ -27,7 +27,6 @@ The C oracle stops at 64 agents, so engines with more are checked against the re
 
 Everything runs under the pinned tie-break of oracle/ref_runner.py (lowest agent id among equal-depth predecessors).
 """
-import importlib.util
 import json
 import os
 import sys
@@ -40,6 +39,7 @@ for p in (os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 import collision_scenarios as cs  # noqa: E402
+import pins  # noqa: E402
 import ref_runner as rr  # noqa: E402
 import wide_fixtures as wf  # noqa: E402
 
@@ -63,13 +63,6 @@ TRACES = {
 }
 STRADDLE_KW = dict(_COMMON, **_SMALL, n_agents=127, request_queue_size=40, max_steps=500, reward_type=2)
 STRADDLE_SEED = 2026
-
-
-def _collisions():
-    spec = importlib.util.spec_from_file_location("generate_collisions", os.path.join(os.path.dirname(HERE), "collisions", "generate_collisions.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def reference_env(kw):
@@ -200,7 +193,6 @@ def carry_requested(sc, base):
 
 
 def record_straddle(out_dir=HERE):
-    gc = _collisions()
     env = reference_env(STRADDLE_KW)
     env.reset(seed=STRADDLE_SEED)
     H, W = (int(v) for v in env.grid_size)
@@ -219,7 +211,7 @@ def record_straddle(out_dir=HERE):
     r_rng = np.zeros((n, T, 6), np.uint64)
     obs, classes = [], {}
     for k, sc in enumerate(scen):
-        gc.inject(env, sc, rng_state)
+        pins.inject_reference(env, sc, rng_state)
         cen = cs.census(sc, sc["actions"][0], H, W, cs.shelf_layer_from_xy(sc["shelf_xy"], H, W))
         assert cs.class_matches(cen, sc["claim"]), (sc["variant"], sc["claim"], dict(cen))
         for c, v in cen.items():

@@ -53,6 +53,15 @@ def config_shape(shape, c):
     return out
 
 
+PER_CONFIG = ("r_agent_delivered", "r_rewards_x2", "r_done", "r_steps", "r_inactive")   # what the generator records per configuration
+
+
+def config_view(z, c):
+    """A recorded fixture (tests/golden/handling) under configuration c in the form tests/pins.py replays — r_<field>[scenario, step]:
+    the PER_CONFIG arrays are recorded as [scenario, configuration, step, ...]; `config` says which one this is."""
+    return dict({k: (a[:, c] if k in PER_CONFIG else a) for k, a in z.items()}, config=c)
+
+
 # ------------------------------------------------------------------------------------------------------------------ census
 def _layer(state, H, W):
     if "shelf_layer" in state:

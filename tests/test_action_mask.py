@@ -22,6 +22,8 @@ import numpy as np
 import pytest
 
 import lockstep
+from device_backends import emu_library
+from models import bits, mask_model
 from rware_oracle import OracleVecEnv
 
 import rware_amd
@@ -33,36 +35,6 @@ UP, DOWN, LEFT, RIGHT = 0, 1, 2, 3
 NOOP, FORWARD, TURN_LEFT, TURN_RIGHT, TOGGLE = 0, 1, 2, 3, 4
 CASES = ("wall", "standing_shelf_while_loaded", "agent_ahead", "toggle_valid_unloaded", "toggle_invalid_unloaded",
          "toggle_valid_loaded", "toggle_invalid_loaded", "reset")
-
-
-def mask_model(st, hw):
-    """(byte (B, N) uint8, Counter of the cases met) — the definition at RW_ACTION_MASK_ON, from a get_state() dict and the highway array"""
-    grid = st["grid"]
-    B, _, H, W = grid.shape
-    x, y, d, c = st["agent_x"], st["agent_y"], st["agent_dir"], st["agent_carry"] > 0
-    tx = x + np.array([0, 0, -1, 1])[d]
-    ty = y + np.array([-1, 1, 0, 0])[d]
-    inside = (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
-    cx, cy, e = np.clip(tx, 0, W - 1), np.clip(ty, 0, H - 1), np.arange(B)[:, None]
-    occ = np.where(inside, grid[e, 0, cy, cx], 0)           # the agent standing on the cell ahead, 1-based
-    shelf_t = np.where(inside, grid[e, 1, cy, cx], 0)
-    occ_loaded = (occ > 0) & c[e, np.maximum(occ, 1) - 1]
-    cancel = c & (shelf_t != 0) & ~occ_loaded               # rware/warehouse.py:829-844
-    fwd = inside & ~cancel
-    toggle = np.where(c, hw[y, x] == 0, grid[e, 1, y, x] != 0)   # :893-895, :889-892
-    byte = (1 | 4 | 8 | ((fwd & (occ == 0)) << 1) | (toggle << 4) | ((fwd & (occ > 0)) << 5)).astype(np.uint8)
-    met = Counter({"wall": int((~inside).sum()), "standing_shelf_while_loaded": int((inside & cancel & (occ == 0)).sum()),
-                   "agent_ahead": int((fwd & (occ > 0)).sum()), "toggle_valid_unloaded": int((~c & toggle).sum()),
-                   "toggle_invalid_unloaded": int((~c & ~toggle).sum()), "toggle_valid_loaded": int((c & toggle).sum()),
-                   "toggle_invalid_loaded": int((c & ~toggle).sum())})
-    return byte, met
-
-
-def bits(byte, permissive=False):
-    byte = np.asarray(byte)
-    if permissive:
-        byte = byte | ((byte >> 4) & 2)
-    return ((byte[..., None] >> np.arange(5, dtype=np.uint8)) & 1).astype(bool)
 
 
 def solo_probe(orc, kw):
@@ -165,11 +137,6 @@ SHAPES = [
 ]
 RUNS = [(s, m) for s in SHAPES for m in MODES]
 RUN_IDS = [f"{s[0]}{''.join(f'-{k}{v}' for k, v in s[1].items())}-{m}" for s, m in RUNS]
-
-
-def _emu():
-    from engine_backend import build_emu
-    return build_emu()
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -389,43 +356,43 @@ def check_pipe_fallback(lib):
 @pytest.mark.parametrize("shape,mode", RUNS, ids=RUN_IDS)
 def test_emulated_mask_matches_the_model_and_the_solo_probe(shape, mode):
     env_id, extra, B, env_kw = shape
-    check_lockstep(_emu(), env_id, extra, B, mode, **env_kw)
+    check_lockstep(emu_library(), env_id, extra, B, mode, **env_kw)
 
 
 @pytest.mark.timeout(1500)
 def test_emulated_constructed_states_and_the_follow_chain_bit():
-    check_constructed(_emu())
+    check_constructed(emu_library())
 
 
 @pytest.mark.timeout(1500)
 @pytest.mark.parametrize("mode", MODES)
 def test_emulated_fused_rollout_leaves_the_mask_of_its_last_step(mode):
-    check_rollout(_emu(), "rware-tiny-4ag-v1", 32, mode)
+    check_rollout(emu_library(), "rware-tiny-4ag-v1", 32, mode)
 
 
 @pytest.mark.timeout(1500)
 def test_emulated_masked_reset_state_writes_and_snapshots():
-    check_state_forms(_emu())
+    check_state_forms(emu_library())
 
 
 @pytest.mark.timeout(1500)
 def test_emulated_sharded_env_gathers_the_mask_in_env_order():
-    check_shards(_emu())
+    check_shards(emu_library())
 
 
 @pytest.mark.timeout(1500)
 def test_emulated_mask_combines_with_counters_episode_statistics_and_packed_rows():
-    check_combination(_emu())
+    check_combination(emu_library())
 
 
 @pytest.mark.timeout(1500)
 def test_emulated_off_switch_read_only_and_info_bit():
-    check_off_switch(_emu())
+    check_off_switch(emu_library())
 
 
 @pytest.mark.timeout(1500)
 def test_emulated_pipelined_request_falls_back_to_the_classic_kernel():
-    check_pipe_fallback(_emu())
+    check_pipe_fallback(emu_library())
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -4,9 +4,7 @@ The expected answers in tests/golden/collisions/*.npz were recorded from the unm
 tie-break); here the C oracle, the product sources under host-thread emulation and (GPU-marked) every kernel path of the real engine
 replay them: 4 steps per scenario, every recorded field, exact.  A red test names task, scenario, family, id assignment, step and agent.
 """
-import glob
-import importlib.util
-import json
+import functools
 import os
 from collections import Counter
 
@@ -14,43 +12,26 @@ import numpy as np
 import pytest
 
 import collision_scenarios as cs
+import pins
 import ref_runner as rr
 import rware_amd
+from engine_checks import default_envs_per_workgroup
 from rware_oracle import OracleVecEnv
 
 FIX_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "collisions")
 TASKS = [f"tiny-{n}ag" for n in (2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 16, 17, 19)] + ["small-4ag", "small-16ag"]
-AGENT_FIELDS = ("agent_x", "agent_y", "agent_dir", "agent_carry", "agent_delivered")
+AGENT_FIELDS = pins.AGENT_FIELDS
+FIELDS = AGENT_FIELDS + ("shelf_xy", "queue")     # what check_state compares beside rewards and done: all the generator records
 T = cs.T_STEPS
-_cache = {}
-
-
-def load(task):
-    if task not in _cache:
-        z = dict(np.load(os.path.join(FIX_DIR, f"{task}.npz")))
-        z["meta"] = json.loads(str(z["meta"]))
-        _cache[task] = z
-    return _cache[task]
-
-
-def _generator():
-    spec = importlib.util.spec_from_file_location("generate_collisions", os.path.join(FIX_DIR, "generate_collisions.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+name_of = cs.name_of
+load = functools.partial(pins.load_npz, FIX_DIR)
+check_state = functools.partial(pins.check_state, fields=FIELDS, name_of=name_of)
 
 
 def kwargs_of(task):
     kw = rware_amd.env_kwargs(load(task)["meta"]["env_id"])
     kw["reward_type"] = rware_amd.enums.enum_value(kw["reward_type"])
     return kw
-
-
-def name_of(task, z, k, t):
-    if "describe" in z:     # (a fixture of another directory names its scenarios itself: tests/test_shelf_handling.py)
-        return z["describe"](task, k, t)
-    return (f"{task}, scenario {k} ({cs.FAMILIES[z['family'][k]]} / {z['variant'][k]}, claims {z['claim'][k]}), "
-            f"ids {cs.ID_ASSIGNMENTS[z['ids'][k]]}, step {t}")
 
 
 def step0_census(z, k):
@@ -60,72 +41,11 @@ def step0_census(z, k):
                       cs.shelf_layer_from_xy(z["shelf_xy"][k], H, W))
 
 
-def inject(be, z, idx, seed_reset=True):
-    """Scenarios `idx` of the fixture into the B = len(idx) envs of an oracle or an engine."""
-    B = len(idx)
-    fields = {f: z[f][idx].astype(np.int32) for f in AGENT_FIELDS}
-    fields["queue"] = z["queue"][idx].astype(np.int32)
-    fields["rng"] = z["rng"][idx] if "rng" in z else np.repeat(z["rng0"][None], B, axis=0)     # (one state per scenario, or the reset's)
-    fields.update({f: z[f][idx].astype(np.int32) for f in ("steps", "inactive") if f in z})
-    sxy = np.ascontiguousarray(z["shelf_xy"][idx].astype(np.int32))
-    if isinstance(be, OracleVecEnv):
-        be.reset(seed=z["meta"]["seed"])
-        be.set_state(**fields)
-        be.recalc_grid(sxy)
-        return be.obs()
-    be.reset(seed=[z["meta"]["seed"]] * B)
-    be.set_state(refresh_obs=False, **fields)
-    be.recalc_grid(sxy)
-    return be.observations()
-
-
-def check_state(task, z, idx, t, state, shelf_xy, rew=None, done=None, who=""):
-    """Every recorded field of step t, for the scenarios idx, against what a backend holds; the message names the first miss."""
-    def fail(e, what):
-        raise AssertionError(f"{who}{name_of(task, z, int(idx[e]), t)}: {what}")
-
-    for f in AGENT_FIELDS:
-        got, want = np.asarray(state[f]), z["r_" + f][idx, t]
-        if not np.array_equal(got, want):
-            e, i = [int(v) for v in np.argwhere(got != want)[0]]
-            k = int(idx[e])
-            prev = z[f][k] if t == 0 else z["r_" + f][k, t - 1]
-            verb = "moved" if f in ("agent_x", "agent_y") and want[e, i] == prev[i] else \
-                "did not move" if f in ("agent_x", "agent_y") and got[e, i] == prev[i] else "differs"
-            fail(e, f"agent {i} {verb}: {f} = {int(got[e, i])}, reference {int(want[e, i])} (was {int(prev[i])})")
-    got, want = np.asarray(shelf_xy), z["r_shelf_xy"][idx, t]
-    if not np.array_equal(got, want):
-        e, s = [int(v) for v in np.argwhere((got != want).any(-1))[0]]
-        fail(e, f"shelf {s + 1} at {got[e, s].tolist()}, reference {want[e, s].tolist()}")
-    if not np.array_equal(np.asarray(state["queue"]), z["r_queue"][idx, t]):
-        e = int(np.argwhere((np.asarray(state["queue"]) != z["r_queue"][idx, t]).any(-1))[0, 0])
-        fail(e, f"queue {np.asarray(state['queue'])[e].tolist()}, reference {z['r_queue'][idx, t][e].tolist()}")
-    for f in ("steps", "inactive", "rng") if "r_steps" in z else ():     # (the fixtures that record the counters: tests/golden/handling)
-        if not np.array_equal(np.asarray(state[f]), z["r_" + f][idx, t]):
-            e = int(np.argwhere((np.asarray(state[f]) != z["r_" + f][idx, t]).reshape(len(idx), -1).any(-1))[0, 0])
-            fail(e, f"{f} {np.asarray(state[f])[e].tolist()}, reference {z['r_' + f][idx, t][e].tolist()}")
-    if rew is not None:
-        got, want = np.round(np.asarray(rew, np.float64) * 2).astype(np.int64), z["r_rewards_x2"][idx, t]
-        if not np.array_equal(got, want):
-            e, i = [int(v) for v in np.argwhere(got != want)[0]]
-            fail(e, f"agent {i} reward {got[e, i] / 2}, reference {want[e, i] / 2}")
-    if done is not None and not np.array_equal(np.asarray(done).astype(bool), z["r_done"][idx, t].astype(bool)):
-        e = int(np.argwhere(np.asarray(done).astype(bool) != z["r_done"][idx, t].astype(bool))[0, 0])
-        fail(e, f"done {bool(np.asarray(done)[e])}, reference {bool(z['r_done'][idx, t][e])}")
-
-
-def check_same(task, z, idx, t, what, got, want, who=""):
-    got, want = np.asarray(got), np.asarray(want)
-    if not np.array_equal(got, want):
-        e = int(np.argwhere((got != want).reshape(len(idx), -1).any(-1))[0, 0])
-        i = int(np.argwhere((got[e] != want[e]).reshape(got.shape[1], -1).any(-1))[0, 0]) if got.ndim > 1 else -1
-        raise AssertionError(f"{who}{name_of(task, z, int(idx[e]), t)}: {what} of agent {i} differs from the oracle's")
-
-
-def oracle_run(task, z, idx, kwargs=None):
-    """The oracle on the injected batch: [(obs, rewards, done)] per step, checked against the fixture on the way."""
-    orc = OracleVecEnv(len(idx), **(kwargs or kwargs_of(task)))
-    out = [inject(orc, z, idx)]
+def oracle_run(task, z, idx):
+    """The oracle on the injected batch: [observation of the injected state, (obs, rewards, done) per step], checked against the
+    fixture on the way."""
+    orc = OracleVecEnv(len(idx), **kwargs_of(task))
+    out = [pins.inject(orc, z, idx)]
     for t in range(z["meta"]["steps"]):
         rew, done = orc.step(z["actions"][idx, t].astype(np.int32))
         check_state(task, z, idx, t, orc.get_state(), orc.shelf_xy(), rew, done, who="oracle: ")
@@ -133,51 +53,20 @@ def oracle_run(task, z, idx, kwargs=None):
     return out
 
 
-def engine_run(task, z, idx, fused, who, library=None, kwargs=None, **ctor):
-    """The engine on the injected batch against fixture (every field, every step) and oracle (observations, rewards, done).
-    A fused rollout hands back no state between its steps: there the fixture's rewards and done are compared at every step through
-    the oracle (itself checked against the fixture at every step, just above), observations against the oracle's at every step,
-    and the state against the fixture behind the last step."""
-    ora = oracle_run(task, z, idx, kwargs)
-    env = rware_amd.WarehouseVecEnv(len(idx), autoreset_mode="disabled", library=library, **(kwargs or kwargs_of(task)), **ctor)
-    T = z["meta"]["steps"]
-    try:
-        unpack = env.unpack_obs if ctor.get("obs_format") == "packed" else (lambda o: o)
-        check_same(task, z, idx, 0, "the observation of the injected state", unpack(inject(env, z, idx)), ora[0], who)
-        if fused:
-            obs, rew, term = env.rollout(z["actions"][idx].astype(np.int32).transpose(1, 0, 2))
-            for t in range(T):
-                check_same(task, z, idx, t, "observation (fused rollout)", unpack(obs[t]), ora[t + 1][0], who)
-                check_same(task, z, idx, t, "reward (fused rollout)", rew[t], ora[t + 1][1], who)
-                check_same(task, z, idx, t, "done (fused rollout)", term[t], ora[t + 1][2].astype(bool), who)
-            check_state(task, z, idx, T - 1, env.get_state(), env.shelf_xy(), rew[T - 1], term[T - 1], who)
-        else:
-            for t in range(T):
-                obs, rew, term, trunc, _ = env.step(z["actions"][idx, t].astype(np.int32))
-                check_state(task, z, idx, t, env.get_state(), env.shelf_xy(), rew, term, who)
-                check_same(task, z, idx, t, "observation", unpack(obs), ora[t + 1][0], who)
-                check_same(task, z, idx, t, "reward", rew, ora[t + 1][1], who)
-                if t == 0 and ctor.get("stats"):
-                    want = ((z["actions"][idx, 0] == cs.FORWARD) & (z["r_req_action"][idx, 0] == cs.NOOP)).sum(-1)
-                    check_same(task, z, idx, 0, "failed_moves", env.event_counters()["failed_moves"], want, who)
-        return env.engines[0].info
-    finally:
-        env.close()
+def engine_run(task, z, idx, fused, who, library=None, **ctor):
+    """pins.engine_run against the fixture (every recorded field, every step) and the oracle (observations, rewards, done); with
+    `stats` the failed-move counter behind step 0 against the requests the reference turned down."""
+    def failed_moves(env, t):
+        if t == 0 and ctor.get("stats"):
+            want = ((z["actions"][idx, 0] == cs.FORWARD) & (z["r_req_action"][idx, 0] == cs.NOOP)).sum(-1)
+            pins.check_same(task, z, idx, 0, "failed_moves", env.event_counters()["failed_moves"], want, who, name_of=name_of)
+    return pins.engine_run(task, z, idx, fused, who, kwargs_of(task), oracle_run(task, z, idx), fields=FIELDS, name_of=name_of,
+                           library=library, after_step=failed_moves, **ctor)
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU
-def check_fixture_directory_is_small(fix_dir, tasks):
-    """The size rule of a fixture directory under tests/golden/ (this one, and tests/golden/observations/): one .npz per task, under 2 MB
-    in all, none larger than the largest golden trace."""
-    files = glob.glob(os.path.join(fix_dir, "*.npz"))
-    assert sorted(os.path.basename(f)[:-4] for f in files) == sorted(tasks)
-    golden = os.path.dirname(fix_dir)
-    largest_other = max(os.path.getsize(f) for f in glob.glob(os.path.join(golden, "*.npz")))
-    assert sum(os.path.getsize(f) for f in files) < 2_000_000 and max(os.path.getsize(f) for f in files) <= largest_other
-
-
 def test_fixture_directory_stays_small():
-    check_fixture_directory_is_small(FIX_DIR, TASKS)
+    pins.check_fixture_directory_is_small(FIX_DIR, TASKS)
 
 
 @pytest.mark.parametrize("task", TASKS)
@@ -234,12 +123,8 @@ def test_oracle_matches_reference_fixture(task):
 @pytest.mark.skipif(not rr.reference_available(), reason="/root/reference not present")
 @pytest.mark.parametrize("task", ["tiny-5ag", "tiny-9ag"])
 def test_reference_regenerates_the_committed_fixture(task, tmp_path):
-    gen = _generator()
-    fresh = dict(np.load(gen.record_task(task, str(tmp_path))))
-    z = dict(np.load(os.path.join(FIX_DIR, f"{task}.npz")))
-    assert sorted(fresh) == sorted(z)
-    for k in z:
-        assert fresh[k].dtype == z[k].dtype and fresh[k].tobytes() == z[k].tobytes(), (task, k)
+    gen = pins.load_generator(os.path.join(FIX_DIR, "generate_collisions.py"))
+    pins.assert_regenerates(gen.record_task(task, str(tmp_path)), os.path.join(FIX_DIR, f"{task}.npz"))
 
 
 @pytest.mark.skipif(not rr.reference_available(), reason="/root/reference not present")
@@ -250,11 +135,10 @@ def test_census_predicts_who_moves_in_the_live_reference(task):
     z = load(task)
     meta = z["meta"]
     H, W = meta["H"], meta["W"]
-    gen = _generator()
     env = rr.make_reference_env(meta["env_id"])
     env.reset(seed=meta["seed"])
     for k in range(meta["n"]):
-        gen.inject(env, {f: z[f][k] for f in AGENT_FIELDS + ("shelf_xy", "queue")})
+        pins.inject_reference(env, {f: z[f][k] for f in AGENT_FIELDS + ("shelf_xy", "queue")})
         for t in range(T):
             snap = rr.snapshot(env)
             _, movers = cs.analyse(snap["agent_x"], snap["agent_y"], snap["agent_dir"], snap["agent_carry"], z["actions"][k, t], H, W,
@@ -301,15 +185,7 @@ def test_emulated_engine_matches_reference_fixture(task, build, fused):
 def gpu_batch(z, multiple, ragged=False):
     """All scenarios, shuffled with a fixed seed (different structures share a wavefront), padded with copies of scenario 0 to a
     whole number of `multiple` envs — or, `ragged`, to one env more than that: a partial last workgroup."""
-    idx = np.random.default_rng(11).permutation(z["meta"]["n"])
-    pad = (-len(idx)) % multiple + (1 if ragged else 0)
-    return np.concatenate([idx, np.zeros(pad, idx.dtype)])
-
-
-def default_envs_per_workgroup(task, N):
-    # the table's rule for small batches (csrc/rware_static_table.h): 16 envs up to 4 agents, 8 from 5 on; 9 .. 19 agents on the small
-    # warehouse step on 4-env workgroups below one round of them and roll out on 8 (13 .. 16 agents), the tiny one has 8-env builds only
-    return 16 if N <= 4 else 4 if task.startswith("small") and N >= 9 else 8
+    return pins.pad_batch(np.random.default_rng(11).permutation(z["meta"]["n"]), multiple, ragged)
 
 
 @pytest.mark.gpu

@@ -14,50 +14,14 @@ import pytest
 
 import golden_util as gu
 import lockstep
+from device_backends import emu_library
+from models import EPISODE_BUFFERS, EpisodeModel, same_buffers
 from rware_oracle import OracleVecEnv
 
 import rware_amd
 
-NAMES = ("return", "length", "last_return", "last_length", "count")
 MODES = ["next_step", "same_step", "disabled"]
 P_ACT = [.05, .7, .1, .1, .05]
-
-
-class EpisodeModel:
-    """The five buffers, from (rewards, terminated) per step.  NEXT_STEP: the step after a `terminated` is a reset step."""
-
-    def __init__(self, B, N, mode):
-        self.mode = mode
-        self.v = {"return": np.zeros((B, N), np.float32), "length": np.zeros(B, np.int32), "last_return": np.zeros((B, N), np.float32),
-                  "last_length": np.zeros(B, np.int32), "count": np.zeros(B, np.int32)}
-        self.pending = np.zeros(B, bool)
-
-    def reset(self, mask=None):
-        m = np.ones(len(self.pending), bool) if mask is None else np.asarray(mask, bool)
-        self.v["return"][m] = 0
-        self.v["length"][m] = 0
-        self.pending[m] = False
-
-    def step(self, rewards, terminated):
-        v, rs = self.v, self.pending.copy()
-        v["return"][rs] = 0                       # a reset step: cleared, nothing recorded
-        v["length"][rs] = 0
-        v["return"][~rs] += np.asarray(rewards, np.float32)[~rs]
-        v["length"][~rs] += 1
-        d = ~rs & np.asarray(terminated, bool)
-        v["last_return"][d] = v["return"][d]
-        v["last_length"][d] = v["length"][d]
-        v["count"][d] += 1
-        v["return"][d] = 0
-        v["length"][d] = 0
-        self.pending = d if self.mode == "next_step" else np.zeros_like(d)
-
-
-def same_buffers(got, model, what):
-    for k in NAMES:
-        g, w = np.asarray(got[k]), model.v[k]
-        assert g.dtype == w.dtype and g.shape == w.shape, (k, what, g.dtype, g.shape)
-        assert np.array_equal(g, w), (k, what, np.argwhere(g != w)[:5].tolist())
 
 
 def make_pair(lib, env_id, extra, B, mode, geom=(0, 0), jit=None, **env_kw):
@@ -141,11 +105,6 @@ def replay_golden(name, lib, steps=None, **env_kw):
 # ------------------------------------------------------------------------------------------------------------------------------
 # CPU suite: the product sources on host threads
 # ------------------------------------------------------------------------------------------------------------------------------
-def _emu():
-    from engine_backend import build_emu
-    return build_emu()
-
-
 # (trace, steps replayed, geometry): an IMAGE trace with messages and episode ends, TWO_STAGE (0.5 rewards), GLOBAL rewards
 EMU_GOLDEN = [("img-msg2-tiny-3ag-8layers", 100, {}), ("tiny-4ag-easy-twostage", 60, {"envs_per_workgroup": 4, "threads_per_workgroup": 128}),
               ("medium-2ag-easy", 160, {"envs_per_workgroup": 4, "threads_per_workgroup": 64})]
@@ -161,7 +120,7 @@ def test_the_replayed_golden_traces_contain_an_episode_end():
 @pytest.mark.timeout(1500)
 @pytest.mark.parametrize("name,steps,geom", EMU_GOLDEN)
 def test_emulated_engine_and_model_agree_on_the_references_traces(name, steps, geom):
-    ends, rew = replay_golden(name, _emu(), steps, **geom)
+    ends, rew = replay_golden(name, emu_library(), steps, **geom)
     assert rew > 0 and ends == int(gu.load_fixture(name)[1]["done"][:steps].sum())
 
 
@@ -175,7 +134,7 @@ def test_emulated_engine_and_model_agree_on_the_references_traces(name, steps, g
     ("rware-tiny-4ag-v1", {"max_steps": 12, "reward_type": 2}, 8, (0, 0)),                           # TWO_STAGE (0.5 rewards)
 ])
 def test_emulated_buffers_match_the_model_in_every_autoreset_mode(env_id, extra, B, geom, mode):
-    check_against_model(_emu(), env_id, extra, B, 40, mode, geom)
+    check_against_model(emu_library(), env_id, extra, B, 40, mode, geom)
 
 
 @pytest.mark.timeout(1500)
@@ -183,12 +142,12 @@ def test_emulated_buffers_match_the_model_in_every_autoreset_mode(env_id, extra,
 @pytest.mark.parametrize("env_id,B,geom", [("rware-small-4ag-v1", 16, (0, 0)), ("rware-tiny-2ag-v1", 7, (4, 64))])
 def test_emulated_fused_rollout_keeps_the_order_of_add_record_clear(env_id, B, geom, mode):
     """three episode ends inside ONE launch on every env: step t's write-back and step t + 1's reset path run on different wavefronts"""
-    check_rollout(_emu(), env_id, {"max_steps": 9}, B, mode, geom)
+    check_rollout(emu_library(), env_id, {"max_steps": 9}, B, mode, geom)
 
 
 @pytest.mark.timeout(1500)
 def test_emulated_masked_reset_state_writes_and_snapshots():
-    lib, B, N = _emu(), 16, 4
+    lib, B, N = emu_library(), 16, 4
     kw = lockstep.oracle_kwargs("rware-small-4ag-v1", max_steps=9, reward_type=0)
     env = rware_amd.WarehouseVecEnv(B, library=lib, episode_stats=True, **kw)
     model = EpisodeModel(B, N, "next_step")
@@ -226,9 +185,9 @@ def test_emulated_masked_reset_state_writes_and_snapshots():
     later = env.episode_stats()
     assert later["count"].sum() > before["count"].sum()
     env.restore(snap)
-    assert all(np.array_equal(env.episode_stats()[k], before[k]) for k in NAMES)
+    assert all(np.array_equal(env.episode_stats()[k], before[k]) for k in EPISODE_BUFFERS)
     run(12, 24, o=None)
-    assert all(np.array_equal(env.episode_stats()[k], later[k]) for k in NAMES)
+    assert all(np.array_equal(env.episode_stats()[k], later[k]) for k in EPISODE_BUFFERS)
     env.free_snapshot(snap)
     env.reset(seed=4)      # reset(): running values 0, the records stay
     after = env.episode_stats()
@@ -240,7 +199,7 @@ def test_emulated_masked_reset_state_writes_and_snapshots():
 @pytest.mark.timeout(1500)
 def test_emulated_sharded_env_gathers_its_buffers_in_env_order():
     B = 24
-    env, orc, kw = make_pair(_emu(), "rware-tiny-2ag-v1", {"max_steps": 9}, B, "next_step", devices=[0, 0, 0])
+    env, orc, kw = make_pair(emu_library(), "rware-tiny-2ag-v1", {"max_steps": 9}, B, "next_step", devices=[0, 0, 0])
     assert len(env.engines) == 3
     model = EpisodeModel(B, 2, "next_step")
     rng = np.random.default_rng(9)
@@ -259,7 +218,7 @@ def test_emulated_sharded_env_gathers_its_buffers_in_env_order():
 
 @pytest.mark.timeout(1500)
 def test_emulated_off_switch_and_info_bits():
-    lib, B = _emu(), 16
+    lib, B = emu_library(), 16
     kw = rware_amd.env_kwargs("rware-small-4ag-v1")
     kw["max_steps"] = 6
     off = rware_amd.WarehouseVecEnv(B, library=lib, **kw)
@@ -304,7 +263,7 @@ def test_emulated_statistics_combine_with_counters_and_packed_rows():
     """RW_STATS_ON | RW_OBS_PACKED | RW_EPISODES_ON on one engine: the event counters, the packed rows and the five buffers all hold"""
     B = 8
     kw = lockstep.oracle_kwargs("rware-tiny-2ag-v1", max_steps=8)
-    env = rware_amd.WarehouseVecEnv(B, library=_emu(), episode_stats=True, stats=True, obs_format="packed", **kw)
+    env = rware_amd.WarehouseVecEnv(B, library=emu_library(), episode_stats=True, stats=True, obs_format="packed", **kw)
     orc = OracleVecEnv(B, **kw)
     model = EpisodeModel(B, 2, "next_step")
     rng = np.random.default_rng(3)
@@ -325,7 +284,7 @@ def test_emulated_statistics_combine_with_counters_and_packed_rows():
 @pytest.mark.timeout(1500)
 def test_emulated_pipelined_request_falls_back_to_the_classic_kernel():
     kw = rware_amd.env_kwargs("rware-small-4ag-v1")
-    env = rware_amd.WarehouseVecEnv(32, library=_emu(), episode_stats=True, pipe=True, **kw)
+    env = rware_amd.WarehouseVecEnv(32, library=emu_library(), episode_stats=True, pipe=True, **kw)
     assert env.engines[0].info.pipe_workgroups == 0 and "RW_EPISODES_ON" in env.engines[0].jit_log()
     env.close()
 

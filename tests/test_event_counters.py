@@ -16,6 +16,7 @@ import pytest
 
 import golden_util as gu
 import lockstep
+from device_backends import emu_library
 from rware_oracle import OracleVecEnv
 
 import rware_amd
@@ -176,11 +177,6 @@ def check_switch_snapshot_and_writes(lib):
 # ------------------------------------------------------------------------------------------------------------------------------
 # CPU suite: the product sources on host threads
 # ------------------------------------------------------------------------------------------------------------------------------
-def _emu():
-    from engine_backend import build_emu
-    return build_emu()
-
-
 @pytest.mark.timeout(1500)
 @pytest.mark.parametrize("name,geom,tile,steps", [
     ("tiny-2ag", (4, 64), 1, 150),                 # generic kernel (LDS agent phases)
@@ -191,7 +187,7 @@ def _emu():
     ("msg2-small-4ag", (0, 0), 4, 100),            # actions are [Action, bits...]: the action re-read strides over the message words
 ])
 def test_emulated_engine_counts_what_the_reference_counts(name, geom, tile, steps):
-    assert replay_trace_with_counters(name, _emu(), steps, tile=tile, envs_per_workgroup=geom[0], threads_per_workgroup=geom[1]) == steps
+    assert replay_trace_with_counters(name, emu_library(), steps, tile=tile, envs_per_workgroup=geom[0], threads_per_workgroup=geom[1]) == steps
 
 
 @pytest.mark.timeout(1500)
@@ -203,7 +199,7 @@ def test_emulated_engine_counts_what_the_reference_counts(name, geom, tile, step
     ("rware-large-16ag-v1", {"sensor_range": 2, "max_steps": 10, "reward_type": 0}, 4, (0, 0)),  # BASELINE config 5's kernel
 ])
 def test_emulated_engine_counters_match_oracle_in_every_autoreset_mode(env_id, extra, B, geom, mode):
-    d, f = check_against_oracle(_emu(), env_id, extra, B, 40, mode, geom, p=(.05, .7, .1, .1, .05))
+    d, f = check_against_oracle(emu_library(), env_id, extra, B, 40, mode, geom, p=(.05, .7, .1, .1, .05))
     assert f > 0
 
 
@@ -214,7 +210,7 @@ def test_emulated_engine_counters_match_oracle_in_every_autoreset_mode(env_id, e
     ("rware-small-10ag-v1", {"max_steps": 11}, 8, (0, 0), "disabled"),
 ])
 def test_emulated_fused_rollout_counts_like_single_steps(env_id, extra, B, geom, mode):
-    check_rollout(_emu(), env_id, extra, B, 30, mode, geom)
+    check_rollout(emu_library(), env_id, extra, B, 30, mode, geom)
 
 
 @pytest.mark.timeout(1500)
@@ -224,7 +220,7 @@ def test_emulated_pipelined_build_counts_too(monkeypatch):
     monkeypatch.setenv("RWARE_PIPE_GRID", "2")
     kw = lockstep.oracle_kwargs("rware-small-4ag-v1", max_steps=14)
     B = 96   # 6 chunks of 16 envs on 2 persistent workgroups
-    env = rware_amd.WarehouseVecEnv(B, library=_emu(), stats=True, pipe=True, **kw)
+    env = rware_amd.WarehouseVecEnv(B, library=emu_library(), stats=True, pipe=True, **kw)
     assert env.engines[0].info.pipe_workgroups == 2 and env.engines[0].info.stats == 1
     orc = OracleVecEnv(B, **kw)
     rng = np.random.default_rng(12)
@@ -245,7 +241,7 @@ def test_emulated_sharded_env_gathers_its_counters():
     kw = rware_amd.env_kwargs("rware-tiny-2ag-v1")
     kw["max_steps"] = 12
     B = 24
-    env = rware_amd.WarehouseVecEnv(B, library=_emu(), devices=[0, 0, 0], stats=True, **kw)
+    env = rware_amd.WarehouseVecEnv(B, library=emu_library(), devices=[0, 0, 0], stats=True, **kw)
     assert len(env.engines) == 3
     orc = OracleVecEnv(B, **kw)
     rng = np.random.default_rng(9)
@@ -258,7 +254,7 @@ def test_emulated_sharded_env_gathers_its_counters():
 
 @pytest.mark.timeout(1500)
 def test_emulated_counters_switch_snapshot_and_writes():
-    check_switch_snapshot_and_writes(_emu())
+    check_switch_snapshot_and_writes(emu_library())
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -16,7 +16,8 @@ import pytest
 
 import golden_util as gu
 import lockstep
-from engine_backend import build_emu
+from device_backends import BACKENDS, GENERIC, GUARD, POISON, emu_library
+from models import ALL7, PLAIN
 from rware_oracle import OracleVecEnv
 
 import rware_amd
@@ -24,43 +25,7 @@ from rware_amd import _capi
 from rware_amd.vector_env import global_image_from_state
 
 P_ACT = [.05, .7, .1, .1, .05]
-GENERIC = dict(jit="off", envs_per_workgroup=4, threads_per_workgroup=64)   # the generic kernel on 4-env workgroups
-PLAIN = [0, 1, 2, 5, 6]          # the layers that never raise
-ALL7 = [0, 1, 2, 3, 4, 5, 6]
 F32, U8 = np.dtype(np.float32), np.dtype(np.uint8)
-POISON, GUARD = 0xA5, 64
-
-
-class Host:
-    """"device" arrays of the host-thread build: numpy arrays"""
-    gpu = False
-    kw = GENERIC
-    library = staticmethod(build_emu)
-
-    @staticmethod
-    def alloc(nbytes):
-        raw = np.full(nbytes + 16, POISON, np.uint8)
-        off = (-raw.ctypes.data) % 16
-        return raw, raw.ctypes.data + off, lambda: raw[off:off + nbytes].copy()
-
-
-class Gpu:
-    """device arrays of the real library: torch tensors, complete before an engine on a stream of its own writes them"""
-    gpu = True
-    kw = {}
-    library = staticmethod(lambda: None)
-
-    @staticmethod
-    def alloc(nbytes):
-        import torch
-
-        t = torch.full((nbytes,), POISON, dtype=torch.uint8, device="cuda")
-        torch.cuda.synchronize()
-        assert t.data_ptr() % 16 == 0
-        return t, t.data_ptr(), lambda: t.cpu().numpy()
-
-
-BACKENDS = [pytest.param(Host, id="emulated"), pytest.param(Gpu, id="gpu", marks=pytest.mark.gpu)]
 
 
 def device_image(be, eng, layers, pad=None, dtype=F32, shift=0):
@@ -302,7 +267,7 @@ def test_two_agents_on_one_cell_and_a_carried_requested_shelf(backend):
 
 # ------------------------------------------------------------------------------------------------ 5. arguments
 def test_the_entry_point_checks_its_arguments():
-    env = rware_amd.WarehouseVecEnv(6, library=build_emu(), **dict(rware_amd.env_kwargs("rware-tiny-2ag-v1"), **GENERIC))
+    env = rware_amd.WarehouseVecEnv(6, library=emu_library(), **dict(rware_amd.env_kwargs("rware-tiny-2ag-v1"), **GENERIC))
     eng = env.engines[0]
     env.reset(seed=1)
     out = np.full(6 * 8 * 16 * 16 + 16, 7.0, np.float32)
@@ -344,7 +309,7 @@ def test_the_entry_point_checks_its_arguments():
 
 
 def test_get_global_image_keeps_its_cache_beside_the_device_form():
-    env = rware_amd.WarehouseVecEnv(4, library=build_emu(), **dict(rware_amd.env_kwargs("rware-tiny-2ag-v1"), **GENERIC))
+    env = rware_amd.WarehouseVecEnv(4, library=emu_library(), **dict(rware_amd.env_kwargs("rware-tiny-2ag-v1"), **GENERIC))
     env.reset(seed=3)
     first = env.get_global_image(PLAIN)
     env.step(np.ones((4, 2), np.int32))

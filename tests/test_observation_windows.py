@@ -6,8 +6,7 @@ and the PCG64 words after each step.  Here the C oracle, the product sources und
 kernel path of the real engine replay them, exact.  A red test names task, scenario, family, step, agent and the window cell
 (row, column, field) of the first differing element.
 """
-import importlib.util
-import json
+import functools
 import os
 from collections import Counter
 
@@ -15,9 +14,10 @@ import numpy as np
 import pytest
 
 import observation_scenarios as osc
+import pins
 import ref_runner as rr
 import rware_amd
-import test_collision_structures as tcs
+from device_backends import emu_library
 from rware_amd import _capi
 from rware_amd.vector_env import global_image_from_state
 from rware_oracle import OracleVecEnv
@@ -32,35 +32,25 @@ TASKS = FLATTENED_TASKS + IMAGE_TASKS
 REGISTERED = {"tiny-4ag": 16, "tiny-9ag": 8, "tiny-19ag": 8}   # ahead-of-time builds of the registered ids: envs per workgroup
 RUNTIME_TASKS = ["tiny-3ag-sr2", "tiny-3ag-sr3", "tiny-3ag-sr4", "tiny-2ag-sr5", "tiny-3ag-msg1", "tiny-3ag-msg2", "tiny-3ag-msg3-sr2",
                  "29x28-10ag", "img-tiny-3ag-directional-sr2"] + LAYOUT_TASKS
-AGENT_FIELDS = tcs.AGENT_FIELDS
+AGENT_FIELDS = pins.AGENT_FIELDS
 T = osc.T_STEPS
-_cache = {}
 
 
-def load(task):
-    """The fixture with its observations unpacked: z["obs"] (n, 3, N, ...) float32, z["features"] (IMAGE_DICT)."""
-    if task not in _cache:
-        z = dict(np.load(os.path.join(FIX_DIR, f"{task}.npz")))
-        meta = z["meta"] = json.loads(str(z["meta"]))
-        shape = tuple(meta["obs_shape"])
-        if "obs_bits" in z:
-            bits = np.unpackbits(z["obs_bits"], axis=-1)[..., :shape[-1] - 2]
-            z["obs"] = np.concatenate([z["obs_xy"], bits.astype(np.float32)], axis=-1)
-        else:
-            n_el = int(np.prod(shape[1:]))
-            flat = np.unpackbits(z["img_bits"], axis=-1)[..., :n_el] if "img_bits" in z else z["img_u8"]
-            z["obs"] = flat.astype(np.float32).reshape(flat.shape[:2] + shape)
-        z["features"] = z["feat_u8"].astype(np.float32) if "feat_u8" in z else None
-        z["agent_delivered"] = np.zeros_like(z["agent_x"])
-        _cache[task] = z
-    return _cache[task]
+def unpack_observations(z):
+    """z["obs"] (n, 3, N, ...) float32, z["features"] (IMAGE_DICT, else None); the flags the generator clears and does not store."""
+    shape = tuple(z["meta"]["obs_shape"])
+    if "obs_bits" in z:
+        bits = np.unpackbits(z["obs_bits"], axis=-1)[..., :shape[-1] - 2]
+        z["obs"] = np.concatenate([z["obs_xy"], bits.astype(np.float32)], axis=-1)
+    else:
+        n_el = int(np.prod(shape[1:]))
+        flat = np.unpackbits(z["img_bits"], axis=-1)[..., :n_el] if "img_bits" in z else z["img_u8"]
+        z["obs"] = flat.astype(np.float32).reshape(flat.shape[:2] + shape)
+    z["features"] = z["feat_u8"].astype(np.float32) if "feat_u8" in z else None
+    z["agent_delivered"] = np.zeros_like(z["agent_x"])
 
 
-def _generator():
-    spec = importlib.util.spec_from_file_location("generate_observations", os.path.join(FIX_DIR, "generate_observations.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+load = functools.partial(pins.load_npz, FIX_DIR, prepare=unpack_observations)
 
 
 def kwargs_of(task, reward_type=None):
@@ -136,42 +126,12 @@ def check_obs(task, z, idx, t, got, who, features=True):
 
 
 def check_state(task, z, idx, t, state, shelf_xy, rew, done, who):
-    def fail(e, what):
-        raise AssertionError(f"{who}{name_of(task, z, int(idx[e]), t)}: {what}")
-
-    fields = AGENT_FIELDS + (("agent_msg",) if z["meta"]["M"] else ())
-    for f in fields:
-        got, want = np.asarray(state[f]), z["r_" + f][idx, t]
-        if not np.array_equal(got, want):
-            e, i = [int(v) for v in np.argwhere(got != want)[0]]
-            fail(e, f"agent {i}: {f} = {int(got[e, i])}, reference {int(want[e, i])}")
-    got, want = np.asarray(shelf_xy), z["r_shelf_xy"][idx, t]
-    if not np.array_equal(got, want):
-        e, s = [int(v) for v in np.argwhere((got != want).any(-1))[0]]
-        fail(e, f"shelf {s + 1} at {got[e, s].tolist()}, reference {want[e, s].tolist()}")
-    got, want = np.asarray(state["queue"]), z["r_queue"][idx, t]
-    if not np.array_equal(got, want):
-        e = int(np.argwhere((got != want).any(-1))[0, 0])
-        fail(e, f"queue {got[e].tolist()}, reference {want[e].tolist()} (the replacement draws follow the goal list's order)")
-    got, want = np.asarray(state["rng"]).astype(np.uint64), z["r_rng"][idx, t]
-    if not np.array_equal(got, want):
-        e = int(np.argwhere((got != want).any(-1))[0, 0])
-        fail(e, f"PCG64 words {got[e].tolist()}, reference {want[e].tolist()}")
-    check_rewards(task, z, idx, t, rew, done, who)
+    """Every recorded field: the agents (with their message where the task has message bits), shelves, queue, PCG64 words, rewards, done."""
+    fields = AGENT_FIELDS + (("agent_msg",) if z["meta"]["M"] else ()) + ("shelf_xy", "queue", "rng")
+    pins.check_state(task, z, idx, t, state, shelf_xy, rew, done, who, fields=fields, name_of=name_of)
 
 
-def check_rewards(task, z, idx, t, rew, done, who):
-    def fail(e, what):
-        raise AssertionError(f"{who}{name_of(task, z, int(idx[e]), t)}: {what}")
-
-    if rew is not None:
-        got, want = np.round(np.asarray(rew, np.float64) * 2).astype(np.int64), z["r_rewards_x2"][idx, t]
-        if not np.array_equal(got, want):
-            e, i = [int(v) for v in np.argwhere(got != want)[0]]
-            fail(e, f"agent {i} reward {got[e, i] / 2}, reference {want[e, i] / 2}")
-    if done is not None and not np.array_equal(np.asarray(done).astype(bool), z["r_done"][idx, t].astype(bool)):
-        e = int(np.argwhere(np.asarray(done).astype(bool) != z["r_done"][idx, t].astype(bool))[0, 0])
-        fail(e, f"done {bool(np.asarray(done)[e])}, reference {bool(z['r_done'][idx, t][e])}")
+check_rewards = functools.partial(pins.check_rewards, name_of=name_of)
 
 
 def reward_groups(z, idx):
@@ -189,7 +149,7 @@ def actions_of(z, idx, t=None):
 def oracle_run(task, z, idx):
     for rt, sub in reward_groups(z, idx):
         orc = OracleVecEnv(len(sub), **kwargs_of(task, rt))
-        check_obs(task, z, sub, -1, tcs.inject(orc, z, sub), "oracle: ")
+        check_obs(task, z, sub, -1, pins.inject(orc, z, sub), "oracle: ")
         for t in range(T):
             rew, done = orc.step(actions_of(z, sub, t))
             check_state(task, z, sub, t, orc.get_state(), orc.shelf_xy(), rew, done, "oracle: ")
@@ -200,9 +160,7 @@ def batch_of(sub, E=1, multiple=1, ragged=False):
     """The scenarios `sub` repeated E times, copy r rolled by r places — every scenario at every env slot of an E-env workgroup, every
     window row at every bit alignment its lane admits — padded with copies of the first one to a whole number of `multiple` envs
     (`ragged`: one env more, a partial last workgroup)."""
-    rows = np.concatenate([np.roll(sub, r) for r in range(E)])
-    pad = (-len(rows)) % multiple + (1 if ragged else 0)
-    return np.concatenate([rows, np.full(pad, sub[0], rows.dtype)])
+    return pins.pad_batch(np.concatenate([np.roll(sub, r) for r in range(E)]), multiple, ragged, fill=sub[0])
 
 
 def engine_run(task, z, idx, fused, who, library=None, E=1, multiple=1, ragged=False, check_info=None, **ctor):
@@ -227,7 +185,7 @@ def engine_run(task, z, idx, fused, who, library=None, E=1, multiple=1, ragged=F
             if check_info is not None:
                 check_info(env.engines[0].info)
             unpack = env.unpack_obs if ctor.get("obs_format") == "packed" else (lambda o: o)
-            check_obs(task, z, rows, -1, unpack(tcs.inject(env, z, rows)), who)
+            check_obs(task, z, rows, -1, unpack(pins.inject(env, z, rows)), who)
             if fused:
                 out = env.rollout(actions_of(z, rows).transpose((1, 0, 2, 3) if z["meta"]["M"] else (1, 0, 2)))
                 obs, rew, term = out[0], out[1], out[2]
@@ -252,7 +210,7 @@ def engine_run(task, z, idx, fused, who, library=None, E=1, multiple=1, ragged=F
 
 # ------------------------------------------------------------------------------------------------------------------ CPU
 def test_fixture_directory_stays_small():
-    tcs.check_fixture_directory_is_small(FIX_DIR, TASKS)
+    pins.check_fixture_directory_is_small(FIX_DIR, TASKS)
 
 
 @pytest.mark.parametrize("task", TASKS)
@@ -332,12 +290,8 @@ def test_oracle_matches_reference_fixture(task):
 @pytest.mark.skipif(not rr.reference_available(), reason="/root/reference not present")
 @pytest.mark.parametrize("task", ["tiny-3ag-msg2", "img-tiny-3ag-directional-sr2", "layout-3goals"])
 def test_reference_regenerates_the_committed_fixture(task, tmp_path):
-    gen = _generator()
-    fresh = dict(np.load(gen.record_task(task, str(tmp_path))))
-    z = dict(np.load(os.path.join(FIX_DIR, f"{task}.npz")))
-    assert sorted(fresh) == sorted(z)
-    for k in z:
-        assert fresh[k].dtype == z[k].dtype and fresh[k].tobytes() == z[k].tobytes(), (task, k)
+    gen = pins.load_generator(os.path.join(FIX_DIR, "generate_observations.py"))
+    pins.assert_regenerates(gen.record_task(task, str(tmp_path)), os.path.join(FIX_DIR, f"{task}.npz"))
 
 
 def emulated_subset(task, z, limit):
@@ -372,19 +326,17 @@ def test_emulated_engine_matches_reference_fixture(task, build, fused):
     """The product sources on host threads, on a subset that still holds every census class, family, id assignment and reward type
     (asserted in `emulated_subset`): the generic kernel, and the ahead-of-time build of the registered ids — register exchange
     (4 agents) and per-cell LDS exchange (9, 19), per step and, one task of each exchange kind, as a fused rollout."""
-    from engine_backend import build_emu
     z = load(task)
     idx = emulated_subset(task, z, EMU_LIMIT.get(task, 112))
     geom = dict(envs_per_workgroup=4, threads_per_workgroup=64, multiple=4) if build == "generic" else dict(multiple=16)
 
     def info(i):
         assert (i.build_kind == 0) == (build == "generic"), i.build_kind
-    engine_run(task, z, idx, fused, f"emulated {build} kernel: ", library=build_emu(), check_info=info, **geom)
+    engine_run(task, z, idx, fused, f"emulated {build} kernel: ", library=emu_library(), check_info=info, **geom)
 
 
 def test_more_than_16_goals_are_refused():
-    from engine_backend import build_emu
-    kw = dict(shelf_columns=0, column_height=0, shelf_rows=0, n_agents=3, request_queue_size=3, max_steps=50, library=build_emu())
+    kw = dict(shelf_columns=0, column_height=0, shelf_rows=0, n_agents=3, request_queue_size=3, max_steps=50, library=emu_library())
     rows = [".xxxxxxxx.", "gggggggggg"]
     with pytest.raises(_capi.EngineError) as ei:
         rware_amd.WarehouseVecEnv(4, layout="\n".join([rows[0], rows[1][:9] + ".", "gggggggg.."]), **kw)
@@ -491,8 +443,7 @@ def test_gpu_opt_in_build_matches_reference_fixture(task):
 
 def _layout_env(task, backend, B, **ctor):
     if backend == "emulated":
-        from engine_backend import build_emu
-        ctor.update(library=build_emu(), envs_per_workgroup=4, threads_per_workgroup=64)
+        ctor.update(library=emu_library(), envs_per_workgroup=4, threads_per_workgroup=64)
     return rware_amd.WarehouseVecEnv(B, autoreset_mode="disabled", **kwargs_of(task), **ctor)
 
 
@@ -507,7 +458,7 @@ def test_global_image_goals_layer_on_the_injected_states(task, backend):
     rows = batch_of(idx, multiple=4)
     env = _layout_env(task, backend, len(rows))
     try:
-        tcs.inject(env, z, rows)
+        pins.inject(env, z, rows)
         want = global_image_from_state(env.get_state(), env.goals, [GOALS])
         assert want.sum() == len(rows) * len(env.goals)
         for dtype in ("float32", "uint8"):

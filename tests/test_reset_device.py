@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 import lockstep
-from engine_backend import build_emu
+from device_backends import BACKENDS, GENERIC, Gpu, Host
+from models import everything, same_everything
 from rware_oracle import OracleVecEnv
 
 import rware_amd
@@ -23,50 +24,12 @@ M64 = (1 << 64) - 1
 # 0, 1, the last one-word seed, the first with a high entropy word, another of those, the sign bit of an int64, all ones
 SPECIAL = [0, 1, 2**32 - 1, 2**32, 2**32 + 5, 2**63, 2**64 - 1]
 P_ACT = [.05, .7, .1, .1, .05]
-GENERIC = dict(jit="off", envs_per_workgroup=4, threads_per_workgroup=64)   # the generic kernel on 4-env workgroups
 
 
 def numpy_state(seed):
     st = np.random.PCG64(np.random.SeedSequence(int(seed))).state["state"]
     s, inc = st["state"], st["inc"]
     return np.array([s >> 64, s & M64, inc >> 64, inc & M64, 0, 0], dtype=np.uint64)
-
-
-class Host:
-    """"device" arrays of the host-thread build: the numpy array itself"""
-    library = staticmethod(build_emu)
-
-    def __init__(self):
-        self.keep = []
-
-    def ptr(self, a):
-        if a is None:
-            return 0
-        a = np.ascontiguousarray(a)
-        self.keep.append(a)
-        return a.ctypes.data
-
-
-class Gpu:
-    """device arrays of the real library: torch tensors, complete before an engine on a stream of its own reads them"""
-    library = staticmethod(lambda: None)
-
-    def __init__(self):
-        self.keep = []
-
-    def ptr(self, a):
-        import torch
-
-        if a is None:
-            return 0
-        a = np.ascontiguousarray(a)
-        t = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).cuda()
-        torch.cuda.synchronize()
-        self.keep.append(t)
-        return t.data_ptr()
-
-
-BACKENDS = [pytest.param(Host, id="emulated"), pytest.param(Gpu, id="gpu", marks=pytest.mark.gpu)]
 
 
 def make_env(be, env_id, B, **kw):
@@ -117,25 +80,6 @@ TWINS = {
     "image-uint8": ("rware-tiny-2ag-v1", 12, dict(GENERIC, observation_type=rware_amd.ObservationType.IMAGE, obs_format="uint8", **OPT_IN)),
     "packed": ("rware-tiny-2ag-v1", 12, dict(GENERIC, obs_format="packed", **OPT_IN)),
 }
-
-
-def everything(env):
-    """every state field and every output / opt-in buffer the engine has, as host arrays"""
-    eng = env.engines[0]
-    out = dict(env.get_state())
-    names = [eng.obs_name, "rewards", "terminated", "truncated", "need_reset", "features"]
-    names += ["action_mask"] * eng.action_mask + ["stat_deliveries", "stat_failed_moves"] * eng.stats
-    for n in names:
-        out["buf:" + n] = eng.read(n)
-    return out
-
-
-def same_everything(a, b, what):
-    ea, eb = everything(a), everything(b)
-    assert ea.keys() == eb.keys()
-    for k in ea:
-        assert ea[k].dtype == eb[k].dtype and np.array_equal(ea[k], eb[k]), (what, k, np.argwhere(ea[k] != eb[k])[:5].tolist())
-    return ea
 
 
 def warm_pair(be, env_id, B, kw, max_steps=6, mode="next_step", seed=3, steps=4):

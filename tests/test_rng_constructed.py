@@ -8,32 +8,31 @@ Generator.choice, value and all six state words); the unmodified reference recor
 (generate_rng_edges.py), which the oracle, the product sources under host-thread emulation and (GPU-marked) every kernel path replay.
 Everything is compared exactly; a red test names task, scenario, claim, field and index.
 """
-import glob
-import importlib.util
-import json
+import functools
 import os
 
 import numpy as np
 import pytest
 
+import pins
 import ref_runner as rr
 import rng_states as rs
 import rware_amd
+from device_backends import emu_library
 from lockstep import lockstep, oracle_kwargs, same_obs, same_state
 from rware_oracle import OracleVecEnv, lib
 
 FIX_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rng_edges")
 TASKS = list(rs.TASKS)
 REGISTERED = [t for t in TASKS if not rs.TASKS[t][1]]
-_cache = {}
 
 
-def load(task):
-    if task not in _cache:
-        z = dict(np.load(os.path.join(FIX_DIR, f"{task}.npz")))
-        z["meta"] = json.loads(str(z["meta"]))
-        _cache[task] = z
-    return _cache[task]
+def delivery_step_as_step_0(z):
+    """the one step of the delivery scenarios in the form pins.check_rewards reads: r_<field>[scenario, step]"""
+    z["r_rewards_x2"], z["r_done"] = z["dl_r_rewards_x2"][:, None], z["dl_r_done"][:, None]
+
+
+load = functools.partial(pins.load_npz, FIX_DIR, prepare=delivery_step_as_step_0)
 
 
 def kwargs_of(task, **extra):
@@ -127,11 +126,7 @@ def test_sampling_states_match_numpy_and_take_their_branch(pop, k):
 
 # ------------------------------------------------------------------------------------------------------------------ the fixture
 def test_fixture_directory_stays_small():
-    files = glob.glob(os.path.join(FIX_DIR, "*.npz"))
-    assert sorted(os.path.basename(f)[:-4] for f in files) == sorted(TASKS)
-    golden = os.path.dirname(FIX_DIR)
-    largest_other = max(os.path.getsize(f) for f in glob.glob(os.path.join(golden, "*.npz")))
-    assert sum(os.path.getsize(f) for f in files) < 1_000_000 and max(os.path.getsize(f) for f in files) <= largest_other
+    pins.check_fixture_directory_is_small(FIX_DIR, TASKS, limit=1_000_000)
 
 
 @pytest.mark.parametrize("task", TASKS)
@@ -195,14 +190,8 @@ def test_the_three_reward_types_and_a_single_candidate_are_in_the_fixture():
 @pytest.mark.skipif(not rr.reference_available(), reason="/root/reference not present")
 @pytest.mark.parametrize("task", ["tiny-2ag", "one-candidate", "prime-candidates"])
 def test_reference_regenerates_the_committed_fixture(task, tmp_path):
-    spec = importlib.util.spec_from_file_location("generate_rng_edges", os.path.join(FIX_DIR, "generate_rng_edges.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    fresh = dict(np.load(gen.record_task(task, str(tmp_path))))
-    z = dict(np.load(os.path.join(FIX_DIR, f"{task}.npz")))
-    assert sorted(fresh) == sorted(z)
-    for k in z:
-        assert fresh[k].dtype == z[k].dtype and fresh[k].tobytes() == z[k].tobytes(), (task, k)
+    gen = pins.load_generator(os.path.join(FIX_DIR, "generate_rng_edges.py"))
+    pins.assert_regenerates(gen.record_task(task, str(tmp_path)), os.path.join(FIX_DIR, f"{task}.npz"))
 
 
 # ------------------------------------------------------------------------------------------------------------------ replay
@@ -210,9 +199,9 @@ RESET_FIELDS = ("agent_x", "agent_y", "agent_dir", "queue", "rng")
 DELIVERY_FIELDS = ("queue", "agent_delivered", "rng")
 
 
-def _fail(task, z, kind, k, what):
+def name_of(task, z, kind, k):
     m = z["meta"]
-    raise AssertionError(f"{task}, {kind} scenario {k} ({m[kind + '_names'][k]}, claims {m[kind + '_claims'][k]}): {what}")
+    return f"{task}, {kind} scenario {k} ({m[kind + '_names'][k]}, claims {m[kind + '_claims'][k]})"
 
 
 def check_fields(task, z, kind, idx, state, fields, who, rew=None, done=None):
@@ -222,16 +211,9 @@ def check_fields(task, z, kind, idx, state, fields, who, rew=None, done=None):
         if not np.array_equal(got, want):
             bad = np.argwhere((got != want).reshape(len(idx), -1))[0]
             e, i = int(bad[0]), int(bad[1])
-            _fail(task, z, kind, int(idx[e]), f"{who}{f}[{i}] = {got[e].reshape(-1)[i]}, reference {want[e].reshape(-1)[i]} "
-                  f"(whole field {got[e].tolist()}, reference {want[e].tolist()})")
-    if rew is not None:
-        got, want = np.round(np.asarray(rew, np.float64) * 2).astype(np.int64), z["dl_r_rewards_x2"][idx]
-        if not np.array_equal(got, want):
-            e, i = [int(v) for v in np.argwhere(got != want)[0]]
-            _fail(task, z, kind, int(idx[e]), f"{who}agent {i} reward {got[e, i] / 2}, reference {want[e, i] / 2}")
-    if done is not None and not np.array_equal(np.asarray(done).astype(bool), z["dl_r_done"][idx].astype(bool)):
-        e = int(np.argwhere(np.asarray(done).astype(bool) != z["dl_r_done"][idx].astype(bool))[0, 0])
-        _fail(task, z, kind, int(idx[e]), f"{who}done {bool(np.asarray(done)[e])}, reference {bool(z['dl_r_done'][idx][e])}")
+            raise AssertionError(f"{who}{name_of(task, z, kind, int(idx[e]))}: {f}[{i}] = {got[e].reshape(-1)[i]}, reference "
+                                 f"{want[e].reshape(-1)[i]} (whole field {got[e].tolist()}, reference {want[e].tolist()})")
+    pins.check_rewards(task, z, idx, 0, rew, done, who, name_of=lambda task, z, k, t: name_of(task, z, kind, k))
 
 
 def delivery_fields(z, idx, rng=None, **extra):
@@ -244,14 +226,7 @@ def delivery_fields(z, idx, rng=None, **extra):
 
 
 def inject_delivery(be, z, idx, **extra):
-    fields, sxy = delivery_fields(z, idx, **extra)
-    if isinstance(be, OracleVecEnv):
-        be.set_state(**fields)
-        be.recalc_grid(sxy)
-        return be.obs()
-    be.set_state(refresh_obs=False, **fields)
-    be.recalc_grid(sxy)
-    return be.observations()
+    return pins.write_state(be, *delivery_fields(z, idx, **extra))
 
 
 def oracle_run(task, z, ir, idl):
@@ -307,10 +282,8 @@ def batch(z, multiple, ragged=False):
     """(reset scenario per env, delivery scenario per env): all of both, shuffled with a fixed seed, padded with copies of scenario 0
     to a whole number of `multiple` envs — or, `ragged`, to one env more: a partial last workgroup."""
     nr, nd = z["meta"]["n_reset"], z["meta"]["n_delivery"]
-    B = max(nr, nd)
-    B += (-B) % multiple + (1 if ragged else 0)
     g = np.random.default_rng(13)
-    pad = lambda n: np.concatenate([g.permutation(n), np.zeros(B - n, np.int64)])  # noqa: E731
+    pad = lambda n: pins.pad_batch(np.concatenate([g.permutation(n), np.zeros(max(nr, nd) - n, np.int64)]), multiple, ragged)  # noqa: E731
     return pad(nr), pad(nd)
 
 
@@ -329,12 +302,11 @@ def test_oracle_matches_reference_fixture(task):
 def test_emulated_engine_matches_reference_fixture(task, build, rollout):
     """The product's rware_pcg64.h, reset and goal phases on host threads: the generic kernel with a partial last workgroup, and
     ahead-of-time builds (per-step launch and one-step rollout; 9 agents: the agent phase in LDS)."""
-    from engine_backend import build_emu
     z = load(task)
     ir, idl = batch(z, 4, ragged=True) if build == "generic" else batch(z, 16)
     assert len(ir) <= 112
     geom = dict(envs_per_workgroup=4, threads_per_workgroup=64) if build == "generic" else {}
-    info = engine_run(task, z, ir, idl, f"emulated {build} kernel: ", library=build_emu(), rollout=rollout, **geom)
+    info = engine_run(task, z, ir, idl, f"emulated {build} kernel: ", library=emu_library(), rollout=rollout, **geom)
     assert (info.build_kind == 0) == (build == "generic")
 
 
@@ -354,8 +326,7 @@ def test_reset_from_every_builder_state_matches_the_oracle(task, backend):
     assert B % 4 == 1 and B <= 112
     library = None
     if backend == "emulated":
-        from engine_backend import build_emu
-        library = build_emu()
+        library = emu_library()
     orc = OracleVecEnv(B, **kwargs_of(task))
     env = rware_amd.WarehouseVecEnv(B, autoreset_mode="disabled", library=library, envs_per_workgroup=4, threads_per_workgroup=64, **kwargs_of(task))
     try:
@@ -424,8 +395,7 @@ def test_emulated_delivery_draw_and_reset_draws_share_one_stream(task, mode):
     """The terminating step draws the replacement request and (same_step: in the same launch; next_step: in the next one) the reset
     draws, from a state in which the delivery leaves a buffered half that the first reset draw rejects; the terminal observation
     (RW_BUF_FINAL_OBS) is compared too.  The oracle is the reference here: it is pinned on the fixture above."""
-    from engine_backend import build_emu
-    autoreset_run(task, mode, library=build_emu(), B=17, envs_per_workgroup=4, threads_per_workgroup=64)
+    autoreset_run(task, mode, library=emu_library(), B=17, envs_per_workgroup=4, threads_per_workgroup=64)
 
 
 # ------------------------------------------------------------------------------------------------------------------ Q >= S
@@ -452,10 +422,9 @@ def rw_create_refuses(library=None):
 def test_emulated_rw_create_refuses_a_request_queue_as_large_as_the_shelf_count():
     """The library's own check, reached through _capi.Engine (what bench.py and rw_multi users build).  Q == 0 and Q == S - 1 stay
     valid and reset."""
-    from engine_backend import build_emu
-    rw_create_refuses(build_emu())
+    rw_create_refuses(emu_library())
     for q in (0, 3):
-        eng = _engine(q, build_emu())
+        eng = _engine(q, emu_library())
         eng.reset(np.arange(4))
         assert eng.read("queue").shape == (4, q)
         eng.close()

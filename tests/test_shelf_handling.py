@@ -7,7 +7,7 @@ host-thread emulation and (GPU-marked) every kernel path of the real engine repl
 the agents with `has_delivered`, every shelf, the queue, both counters, the generator words, rewards, done — exact.  A red test names
 task, scenario, family, claim, id assignment, reward type, step and agent.
 """
-import importlib.util
+import functools
 import json
 import os
 from collections import Counter
@@ -17,14 +17,15 @@ import pytest
 
 import handling_scenarios as hs
 import lockstep
+import pins
 import ref_runner as rr
 import rng_states as rs
 import rware_amd
-import test_collision_structures as tcs
 import wide_fixtures as wf
+from device_backends import emu_library
+from engine_checks import default_envs_per_workgroup
+from models import EpisodeModel, bits, mask_model, same_buffers
 from rware_oracle import OracleVecEnv
-from test_action_mask import bits, mask_model
-from test_episode_stats import EpisodeModel, same_buffers
 
 FIX_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "handling")
 REGISTERED = [f"tiny-{n}ag" for n in (2, 4, 8, 9, 13, 16, 19)] + ["small-4ag", "small-16ag"]
@@ -33,30 +34,17 @@ TASKS = REGISTERED + ["small-20ag", "29x28-10ag", "layout-5goals", WIDE]
 ORACLE_TASKS = [t for t in TASKS if t != WIDE]
 C = len(hs.CONFIGS)
 T = hs.T_STEPS
-STATE_FIELDS = ("agent_x", "agent_y", "agent_dir", "agent_carry", "agent_delivered")
-PER_CONFIG = ("r_agent_delivered", "r_rewards_x2", "r_done", "r_steps", "r_inactive")   # what the generator records per configuration
+AGENT_FIELDS = pins.AGENT_FIELDS
+FIELDS = AGENT_FIELDS + ("shelf_xy", "queue", "steps", "inactive", "rng")     # what check_state compares beside rewards and done
 OPT_IN = dict(stats=True, episode_stats=True, action_mask=True, time_limit_truncates=True)
-_cache = {}
+_views = {}
 
 
-def load(task):
-    if task not in _cache:
-        z = dict(np.load(os.path.join(FIX_DIR, f"{task}.npz")))
-        z["meta"] = json.loads(str(z["meta"]))
-        if "obs_bits" in z:
-            z["obs"] = wf.unpack_obs(z, "", z["meta"]["obs_shape"])      # (n, 1 + T, N, L): the injected state, then every step
-        for k, a in z.items():
-            if k != "meta":
-                a.setflags(write=False)
-        _cache[task] = z
-    return _cache[task]
+load = functools.partial(pins.load_npz, FIX_DIR, prepare=wf.unpack_scenario_obs)
 
 
-def _generator():
-    spec = importlib.util.spec_from_file_location("generate_handling", os.path.join(FIX_DIR, "generate_handling.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+def generator():
+    return pins.load_generator(os.path.join(FIX_DIR, "generate_handling.py"))
 
 
 def config_name(c):
@@ -65,26 +53,29 @@ def config_name(c):
 
 
 def view(task, c):
-    """The fixture under configuration c in the form tests/test_collision_structures.py replays: r_<field>[scenario, step]."""
+    """The fixture under configuration c in the form tests/pins.py replays: r_<field>[scenario, step]; `config` says which it is."""
     key = (task, c)
-    if key not in _cache:
+    if key not in _views:
         z = load(task)
-        v = {k: a for k, a in z.items() if k not in PER_CONFIG}
-        for k in PER_CONFIG:                         # recorded as [scenario, configuration, step, ...]
-            assert z[k].shape[1:3] == (C, T), (task, k, z[k].shape)
-            v[k] = z[k][:, c]
-        v["describe"] = lambda task, k, t: (f"{task}, scenario {k} ({hs.FAMILIES[z['family'][k]]} / {z['variant'][k]}, claims {z['claim'][k]}), "
-                                            f"ids {hs.ID_ASSIGNMENTS[z['ids'][k]]}, {config_name(c)}, step {t}")
-        _cache[key] = v
-    return _cache[key]
+        assert all(z[k].shape[1:3] == (C, T) for k in hs.PER_CONFIG), task
+        _views[key] = hs.config_view(z, c)
+    return _views[key]
+
+
+def name_of(task, v, k, t):
+    return (f"{task}, scenario {k} ({hs.FAMILIES[v['family'][k]]} / {v['variant'][k]}, claims {v['claim'][k]}), "
+            f"ids {hs.ID_ASSIGNMENTS[v['ids'][k]]}, {config_name(v['config'])}, step {t}")
+
+
+check_state = functools.partial(pins.check_state, fields=FIELDS, name_of=name_of)
+check_same = functools.partial(pins.check_same, name_of=name_of)
 
 
 def kwargs_of(task, c, **more):
     """Constructor arguments of the task under configuration c: ONE dict for the env and the oracle."""
     meta = load(task)["meta"]
-    rt, limited = hs.CONFIGS[c]
     kw = lockstep.oracle_kwargs(meta["env_id"], **meta["overrides"])
-    kw.update(reward_type=rt, **(hs.LIMITS if limited else dict(max_steps=None, max_inactivity_steps=None)))
+    kw.update(hs.config_shape({}, c))     # (the reward type and both limits)
     kw.update(more)
     return kw
 
@@ -100,10 +91,10 @@ def shape_of(task, c=None):
 def states_of(task, k, c):
     """[state before step 0, after step 0, ... after step T - 1] of scenario k under configuration c, as the census reads them."""
     z = load(task)
-    first = dict({f: z[f][k] for f in STATE_FIELDS + ("shelf_xy", "queue", "steps", "inactive")})
+    first = dict({f: z[f][k] for f in AGENT_FIELDS + ("shelf_xy", "queue", "steps", "inactive")})
     out = [first]
     for t in range(T):
-        st = {f: z["r_" + f][k, t] for f in STATE_FIELDS[:4] + ("shelf_xy", "queue")}
+        st = {f: z["r_" + f][k, t] for f in AGENT_FIELDS[:4] + ("shelf_xy", "queue")}
         st.update({f: z["r_" + f][k, c, t] for f in ("agent_delivered", "steps", "inactive")})
         out.append(st)
     return out
@@ -127,17 +118,18 @@ def check_events(task, v, idx, t, deliveries, failed_moves, base, who=""):
         want = rec[idx, :t + 1].sum(1) + base[what]
         if not np.array_equal(np.asarray(got), want):
             e = int(np.argwhere(np.asarray(got) != want)[0, 0])
-            raise AssertionError(f"{who}{tcs.name_of(task, v, int(idx[e]), t)}: {what} {int(np.asarray(got)[e]) - int(base[what][e])} since the injection, "
+            raise AssertionError(f"{who}{name_of(task, v, int(idx[e]), t)}: {what} {int(np.asarray(got)[e]) - int(base[what][e])} since the injection, "
                                  f"reference {int(want[e]) - int(base[what][e])}")
 
 
 def oracle_run(task, c, idx, corrupt=None):
     """The oracle on scenarios idx under configuration c, every field of every step against the fixture — the agents with their flags,
     the shelves, the queue, both counters, the generator words, rewards, done, and its event counters against the recorded counts.
-    `corrupt` = (field, step): one element of that field is changed behind that step, and nothing else (the sensitivity test)."""
+    `corrupt` = (field, step): one element of that field is changed behind that step, and nothing else (the sensitivity test).
+    Returns what pins.engine_run compares an engine with: [observation of the injected state, (obs, rewards, done) per step]."""
     v = view(task, c)
     orc = OracleVecEnv(len(idx), **kwargs_of(task, c))
-    tcs.inject(orc, v, idx)
+    out = [pins.inject(orc, v, idx)]
     base = dict(deliveries=orc.stat_deliveries.copy(), failed_moves=orc.stat_failed_moves.copy())
 
     def bent(field, t, a):
@@ -151,37 +143,20 @@ def oracle_run(task, c, idx, corrupt=None):
         rew, done = orc.step(v["actions"][idx, t].astype(np.int32))
         st = orc.get_state()
         st = {f: bent(f, t, a) for f, a in st.items()}
-        tcs.check_state(task, v, idx, t, st, bent("shelf_xy", t, orc.shelf_xy()), bent("rewards", t, rew), bent("done", t, done), who="oracle: ")
+        check_state(task, v, idx, t, st, bent("shelf_xy", t, orc.shelf_xy()), bent("rewards", t, rew), bent("done", t, done), who="oracle: ")
         check_events(task, v, idx, t, bent("deliveries", t, orc.stat_deliveries), bent("failed_moves", t, orc.stat_failed_moves), base, "oracle: ")
+        out.append((orc.obs(), rew, done))
+    return out
 
 
 def engine_run(task, c, idx, fused, who, library=None, **ctor):
-    """The engine on scenarios idx under configuration c: tests/test_collision_structures.engine_run — every recorded field against the
-    fixture, observations, rewards and done against the oracle, itself checked against the fixture on the way — or, where no oracle
-    exists, the same fields and the observations against the fixture alone."""
+    """The engine on scenarios idx under configuration c: pins.engine_run — every recorded field against the fixture, observations,
+    rewards and done against the oracle, itself checked against the fixture on the way — or, where no oracle exists, against the
+    fixture's own observations."""
     v = view(task, c)
-    who = f"{who}{config_name(c)}: "
-    if load(task)["meta"]["N"] <= 64:
-        return tcs.engine_run(task, v, idx, fused, who, library=library, kwargs=kwargs_of(task, c), **ctor)
-    env = rware_amd.WarehouseVecEnv(len(idx), autoreset_mode="disabled", library=library, **kwargs_of(task, c), **ctor)
-    try:
-        tcs.check_same(task, v, idx, 0, "the observation of the injected state", tcs.inject(env, v, idx), v["obs"][idx, 0], who)
-        acts = v["actions"][idx].astype(np.int32).transpose(1, 0, 2)
-        if fused:
-            obs, rew, term = env.rollout(acts)
-            for t in range(T):
-                tcs.check_same(task, v, idx, t, "observation (fused rollout)", obs[t], v["obs"][idx, t + 1], who)
-                tcs.check_same(task, v, idx, t, "reward (fused rollout)", rew[t] * 2, v["r_rewards_x2"][idx, t], who)
-                tcs.check_same(task, v, idx, t, "done (fused rollout)", term[t], v["r_done"][idx, t].astype(bool), who)
-            tcs.check_state(task, v, idx, T - 1, env.get_state(), env.shelf_xy(), rew[T - 1], term[T - 1], who)
-        else:
-            for t in range(T):
-                obs, rew, term, trunc, _ = env.step(acts[t])
-                tcs.check_state(task, v, idx, t, env.get_state(), env.shelf_xy(), rew, term, who)
-                tcs.check_same(task, v, idx, t, "observation", obs, v["obs"][idx, t + 1], who)
-        return env.engines[0].info
-    finally:
-        env.close()
+    want = oracle_run(task, c, idx) if v["meta"]["N"] <= 64 else pins.fixture_outputs(v, idx)
+    return pins.engine_run(task, v, idx, fused, f"{who}{config_name(c)}: ", kwargs_of(task, c), want, fields=FIELDS, name_of=name_of,
+                           library=library, **ctor)
 
 
 def opt_in_run(task, c, idx, who, library=None, **ctor):
@@ -195,7 +170,7 @@ def opt_in_run(task, c, idx, who, library=None, **ctor):
     B, N = len(idx), v["meta"]["N"]
     env = rware_amd.WarehouseVecEnv(B, autoreset_mode="disabled", library=library, **kwargs_of(task, c), **OPT_IN, **ctor)
     try:
-        tcs.inject(env, v, idx)
+        pins.inject(env, v, idx)
         ev = env.event_counters()
         base = dict(deliveries=ev["deliveries"].copy(), failed_moves=ev["failed_moves"].copy())
         model = EpisodeModel(B, N, "disabled")
@@ -203,21 +178,21 @@ def opt_in_run(task, c, idx, who, library=None, **ctor):
         for k in ("return", "length", "last_return", "last_length", "count"):     # (whatever reset() and the injection left)
             model.v[k][...] = first[k]
         hw = np.asarray(env.highways)
-        tcs.check_same(task, v, idx, 0, "action mask of the injected state", env.action_mask(), bits(mask_model(env.get_state(), hw)[0]), who)
+        check_same(task, v, idx, 0, "action mask of the injected state", env.action_mask(), bits(mask_model(env.get_state(), hw)[0]), who)
         for t in range(T):
             obs, rew, term, trunc, _ = env.step(v["actions"][idx, t].astype(np.int32))
             st = env.get_state()
-            tcs.check_state(task, v, idx, t, st, env.shelf_xy(), rew, term | trunc, who)
+            check_state(task, v, idx, t, st, env.shelf_xy(), rew, term | trunc, who)
             want_term = v["r_inactive"][idx, t] >= hs.LIMITS["max_inactivity_steps"]
             want_trunc = v["r_steps"][idx, t] >= hs.LIMITS["max_steps"]
             assert np.array_equal(want_term | want_trunc, v["r_done"][idx, t].astype(bool))
-            tcs.check_same(task, v, idx, t, "terminated (the inactivity rule)", term, want_term, who)
-            tcs.check_same(task, v, idx, t, "truncated (the step limit)", trunc, want_trunc, who)
+            check_same(task, v, idx, t, "terminated (the inactivity rule)", term, want_term, who)
+            check_same(task, v, idx, t, "truncated (the step limit)", trunc, want_trunc, who)
             ev = env.event_counters()
             check_events(task, v, idx, t, ev["deliveries"], ev["failed_moves"], base, who)
             model.step(v["r_rewards_x2"][idx, t].astype(np.float32) / 2, v["r_done"][idx, t].astype(bool))
             same_buffers(env.episode_stats(), model, f"{who}{task}, step {t}")
-            tcs.check_same(task, v, idx, t, "action mask", env.action_mask(), bits(mask_model(st, hw)[0]), who)
+            check_same(task, v, idx, t, "action mask", env.action_mask(), bits(mask_model(st, hw)[0]), who)
         return env.engines[0].info
     finally:
         env.close()
@@ -232,7 +207,7 @@ def autoreset_run(task, c, idx, mode, who, library=None, **ctor):
     env = rware_amd.WarehouseVecEnv(len(idx), autoreset_mode=mode, library=library, **kw, **ctor)
     orc = OracleVecEnv(len(idx), **kw)
     try:
-        lockstep.same_obs(tcs.inject(env, v, idx), tcs.inject(orc, v, idx), f"{who}{task}: the observation of the injected state")
+        lockstep.same_obs(pins.inject(env, v, idx), pins.inject(orc, v, idx), f"{who}{task}: the observation of the injected state")
         run = lockstep.lockstep(env, orc, v["actions"][idx].astype(np.int32).transpose(1, 0, 2), mode, seed=None, state_every=1)
         assert run.episodes >= len(idx) // 4, (task, mode, run)
         return env.engines[0].info
@@ -242,7 +217,7 @@ def autoreset_run(task, c, idx, mode, who, library=None, **ctor):
 
 # ------------------------------------------------------------------------------------------------------------------ CPU
 def test_fixture_directory_stays_small():
-    tcs.check_fixture_directory_is_small(FIX_DIR, TASKS)
+    pins.check_fixture_directory_is_small(FIX_DIR, TASKS)
 
 
 @pytest.mark.parametrize("task", TASKS)
@@ -254,7 +229,7 @@ def test_fixture_holds_every_class_and_every_scenario_its_claim(task):
     meta, N, S = z["meta"], z["meta"]["N"], z["meta"]["S"]
     scen = hs.build_scenarios(shape_of(task), seed=meta["round_seed"])
     assert len(scen) == meta["n"]
-    for f in STATE_FIELDS + ("shelf_xy", "queue", "steps", "inactive", "rng", "actions"):
+    for f in AGENT_FIELDS + ("shelf_xy", "queue", "steps", "inactive", "rng", "actions"):
         assert np.array_equal(np.stack([sc[f] for sc in scen]), z[f]), (task, f)
     assert [sc["claim"] for sc in scen] == z["claim"].tolist() and [sc["variant"] for sc in scen] == z["variant"].tolist()
     total = [Counter() for _ in range(C)]
@@ -262,7 +237,7 @@ def test_fixture_holds_every_class_and_every_scenario_its_claim(task):
         for c in range(C):
             by_step = census_of(task, k, c)
             assert hs.claim_holds(by_step, str(z["claim"][k]), hs.CONFIGS[c][1]), \
-                f"{view(task, c)['describe'](task, k, 0)}: the census found {[dict(b) for b in by_step]}"
+                f"{name_of(task, view(task, c), k, 0)}: the census found {[dict(b) for b in by_step]}"
             for b in by_step:
                 total[c].update(b)
     assert [dict(sorted(t.items())) for t in total] == meta["census"]
@@ -311,19 +286,14 @@ def test_oracle_matches_reference_fixture(task):
 @pytest.mark.skipif(not rr.reference_available(), reason="/root/reference not present")
 @pytest.mark.parametrize("task", ["tiny-9ag", "layout-5goals"])
 def test_reference_regenerates_the_committed_fixture(task, tmp_path):
-    gen = _generator()
-    fresh = dict(np.load(gen.record_task(task, str(tmp_path))))
-    z = dict(np.load(os.path.join(FIX_DIR, f"{task}.npz")))
-    assert sorted(fresh) == sorted(z)
-    for k in z:
-        assert fresh[k].dtype == z[k].dtype and fresh[k].tobytes() == z[k].tobytes(), (task, k)
+    pins.assert_regenerates(generator().record_task(task, str(tmp_path)), os.path.join(FIX_DIR, f"{task}.npz"))
 
 
 def test_fixtures_hold_every_class_the_golden_traces_hold():
     """The census over every committed trace of the reference (random and scripted play), printed; the constructed fixtures hold every
     class, so at least every class that play reached — now, and when trace_census.json was recorded.  Only the inclusion is asserted:
     a trace added later makes the stored record stale (said in the output, with how to re-record it), not the test red."""
-    gen = _generator()
+    gen = generator()
     with open(os.path.join(FIX_DIR, "trace_census.json")) as f:
         stored = json.load(f)
     per = {name: dict(sorted(gen.trace_census(meta, z).items())) for name, meta, z in gen.golden_traces()}
@@ -449,12 +419,11 @@ def test_emulated_engine_matches_reference_fixture(task, build, fused):
     agent phase up to 8 agents; per-cell exchange for the per-step launches of 9 and 13) — which take an engine with the limits
     overridden — on a subset that holds every class, family, id assignment and configuration.  The whole fixture runs on the oracle
     and on the GPU."""
-    from engine_backend import build_emu
     geom = dict(envs_per_workgroup=4, threads_per_workgroup=64) if build == "generic" else {}
     if task == WIDE:
         geom = dict(envs_per_workgroup=4, threads_per_workgroup=256, jit="off")
     for c, idx in emulated_subset(task):
-        info = engine_run(task, c, idx, fused, f"emulated {build} kernel: ", library=build_emu(), **geom)
+        info = engine_run(task, c, idx, fused, f"emulated {build} kernel: ", library=emu_library(), **geom)
         assert (info.build_kind == 0) == (build == "generic"), (info.build_kind, c)
 
 
@@ -462,29 +431,26 @@ def test_emulated_engine_matches_reference_fixture(task, build, fused):
 @pytest.mark.parametrize("task", ["tiny-4ag", "tiny-8ag", "tiny-13ag"])
 def test_emulated_prefilter_alone_in_its_wavefront(task, fused):
     """wavefront_groups on host threads: 32 scenarios of either group, under every configuration, on the ahead-of-time build."""
-    from engine_backend import build_emu
     for name, idx in wavefront_groups(task).items():
         for c in range(C):
-            info = engine_run(task, c, group_batch(idx, 16, 32), fused, f"emulated static kernel, {name} alone: ", library=build_emu())
+            info = engine_run(task, c, group_batch(idx, 16, 32), fused, f"emulated static kernel, {name} alone: ", library=emu_library())
             assert info.build_kind != 0
 
 
 def test_emulated_opt_in_outputs_match_the_reference_fixture():
     """(the GPU test below, on host threads, for one configuration: the generic kernel carries the opt-in code)"""
-    from engine_backend import build_emu
     z = load("tiny-4ag")
     idx = np.random.default_rng(3).permutation(z["meta"]["n"])[:32]
-    opt_in_run("tiny-4ag", 2, idx, "emulated, opt-in outputs: ", library=build_emu())
+    opt_in_run("tiny-4ag", 2, idx, "emulated, opt-in outputs: ", library=emu_library())
 
 
 @pytest.mark.parametrize("mode", ["next_step", "same_step"])
 def test_emulated_limit_family_under_autoreset(mode):
-    from engine_backend import build_emu
     idx = group_batch(limit_family("tiny-4ag"), 16)       # (all of the family, the copies under the other id assignments included)
-    autoreset_run("tiny-4ag", 0, idx, mode, "emulated: ", library=build_emu())
+    autoreset_run("tiny-4ag", 0, idx, mode, "emulated: ", library=emu_library())
 
 
-SENSITIVE = STATE_FIELDS + ("shelf_xy", "queue", "steps", "inactive", "rng", "rewards", "done", "deliveries", "failed_moves")
+SENSITIVE = AGENT_FIELDS + ("shelf_xy", "queue", "steps", "inactive", "rng", "rewards", "done", "deliveries", "failed_moves")
 
 
 @pytest.mark.parametrize("field", SENSITIVE)
@@ -499,7 +465,7 @@ def test_one_corrupted_element_fails_the_check(field):
         msg = str(err.value)
         assert msg.startswith("oracle: tiny-4ag, scenario ") and f"step {step}" in msg and "reward type 2 (TWO_STAGE)" in msg, msg
         assert all(word in msg for word in ("claims ", "ids ", " / ")), msg
-        if field in STATE_FIELDS + ("rewards",):
+        if field in AGENT_FIELDS + ("rewards",):
             assert "agent " in msg, msg
 
 
@@ -512,7 +478,7 @@ def limit_family(task):
 def gpu_batch(task, multiple, ragged=False):
     """All scenarios, shuffled with a fixed seed (different situations share a wavefront), padded with copies of scenario 0 to a whole
     number of `multiple` envs — or, `ragged`, to one env more than that: a partial last workgroup."""
-    return tcs.gpu_batch(load(task), multiple, ragged)
+    return pins.pad_batch(np.random.default_rng(11).permutation(load(task)["meta"]["n"]), multiple, ragged)
 
 
 @pytest.mark.gpu
@@ -522,7 +488,7 @@ def test_gpu_ahead_of_time_build_matches_reference_fixture(task, fused):
     N = load(task)["meta"]["N"]
     for c in range(C):
         info = engine_run(task, c, gpu_batch(task, 32), fused, "ahead-of-time build: ")
-        assert info.build_kind in (1, 2) and info.jit == 0 and info.envs_per_workgroup == tcs.default_envs_per_workgroup(task, N), \
+        assert info.build_kind in (1, 2) and info.jit == 0 and info.envs_per_workgroup == default_envs_per_workgroup(task, N), \
             (info.build_kind, info.jit, info.envs_per_workgroup)
 
 

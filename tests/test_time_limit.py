@@ -14,8 +14,9 @@ import pytest
 
 import golden_util as gu
 import lockstep
+from device_backends import emu_library
+from models import EpisodeModel, same_buffers
 from rware_oracle import OracleVecEnv
-from test_episode_stats import EpisodeModel, same_buffers
 
 import rware_amd
 
@@ -225,23 +226,18 @@ def replay_golden(name, lib, **env_kw):
 # ------------------------------------------------------------------------------------------------------------------------------
 # CPU suite: the product sources on host threads
 # ------------------------------------------------------------------------------------------------------------------------------
-def _emu():
-    from engine_backend import build_emu
-    return build_emu()
-
-
 @pytest.mark.timeout(1500)
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("env_id,geom,generic", EMU_BUILDS)
 def test_emulated_four_cases_in_one_workgroup(env_id, geom, generic, mode):
-    check_constructed(_emu(), env_id, mode, geom, generic=generic)
+    check_constructed(emu_library(), env_id, mode, geom, generic=generic)
 
 
 @pytest.mark.timeout(1500)
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("env_id,geom,generic", EMU_BUILDS)
 def test_emulated_lockstep_every_end_is_a_truncation(env_id, geom, generic, mode):
-    seen = check_lockstep(_emu(), env_id, {"max_steps": 6}, 12 if generic else 16, 40, mode, geom, generic=generic)
+    seen = check_lockstep(emu_library(), env_id, {"max_steps": 6}, 12 if generic else 16, 40, mode, geom, generic=generic)
     assert seen["term"] == 0 and seen["trunc"] > 0
 
 
@@ -249,7 +245,7 @@ def test_emulated_lockstep_every_end_is_a_truncation(env_id, geom, generic, mode
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("env_id,geom,generic", EMU_BUILDS)
 def test_emulated_lockstep_inactivity_ends_come_first(env_id, geom, generic, mode):
-    seen = check_lockstep(_emu(), env_id, {"max_steps": 9, "max_inactivity_steps": 4}, 12 if generic else 16, 40, mode, geom, generic=generic)
+    seen = check_lockstep(emu_library(), env_id, {"max_steps": 9, "max_inactivity_steps": 4}, 12 if generic else 16, 40, mode, geom, generic=generic)
     assert seen["first_inact"] > 0
 
 
@@ -257,12 +253,12 @@ def test_emulated_lockstep_inactivity_ends_come_first(env_id, geom, generic, mod
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("env_id,geom,generic", EMU_BUILDS[:2])
 def test_emulated_fused_rollout_tapes_the_truncated_flags(env_id, geom, generic, mode):
-    check_rollout(_emu(), env_id, 7 if generic else 16, mode, geom, generic=generic)
+    check_rollout(emu_library(), env_id, 7 if generic else 16, mode, geom, generic=generic)
 
 
 @pytest.mark.timeout(1500)
 def test_emulated_rollout_without_the_flag_keeps_three_elements_and_zero_fills_a_tape():
-    check_rollout_without_the_flag(_emu())
+    check_rollout_without_the_flag(emu_library())
 
 
 @pytest.mark.timeout(1500)
@@ -271,7 +267,7 @@ def test_emulated_rollout_without_the_flag_keeps_three_elements_and_zero_fills_a
     ("medium-2ag-easy", {"envs_per_workgroup": 4, "threads_per_workgroup": 64}, ("trunc",)),   # max_steps 150, no inactivity limit
 ])
 def test_emulated_engine_replays_the_references_traces_with_the_flag(name, geom, kinds):
-    seen = replay_golden(name, _emu(), **geom)
+    seen = replay_golden(name, emu_library(), **geom)
     assert all(seen[k] > 0 for k in kinds) and (seen["term"] == 0 or "term" in kinds)
 
 
@@ -280,7 +276,7 @@ def test_emulated_engine_replays_the_references_traces_with_the_flag(name, geom,
 def test_emulated_truncating_step_records_the_episode(mode):
     """episode_stats=True: the record follows `done`, not `terminated` — EpisodeModel fed with the oracle's done; numpy step()'s info keys"""
     B = 16
-    env, orc, kw = make_pair(_emu(), "rware-small-4ag-v1", {"max_steps": 7, "max_inactivity_steps": 5}, B, mode, episode_stats=True)
+    env, orc, kw = make_pair(emu_library(), "rware-small-4ag-v1", {"max_steps": 7, "max_inactivity_steps": 5}, B, mode, episode_stats=True)
     model = EpisodeModel(B, 4, mode)
     rng = np.random.default_rng(2)
     env.reset(seed=9)
@@ -304,7 +300,7 @@ def test_emulated_truncating_step_records_the_episode(mode):
 @pytest.mark.timeout(1500)
 def test_emulated_resets_snapshots_and_numpy_step():
     B, N = 16, 4
-    env, orc, kw = make_pair(_emu(), "rware-small-4ag-v1", {"max_steps": 6}, B, "disabled")
+    env, orc, kw = make_pair(emu_library(), "rware-small-4ag-v1", {"max_steps": 6}, B, "disabled")
     acts = np.random.default_rng(6).choice(5, size=(20, B, N), p=P_ACT).astype(np.int32)
     env.reset(seed=4)
     for t in range(6):
@@ -332,7 +328,7 @@ def test_emulated_resets_snapshots_and_numpy_step():
 @pytest.mark.timeout(1500)
 def test_emulated_sharded_env_concatenates_the_flags():
     B = 24
-    env, orc, kw = make_pair(_emu(), "rware-tiny-2ag-v1", {"max_steps": 9, "max_inactivity_steps": 6}, B, "next_step", devices=[0, 0, 0])
+    env, orc, kw = make_pair(emu_library(), "rware-tiny-2ag-v1", {"max_steps": 9, "max_inactivity_steps": 6}, B, "next_step", devices=[0, 0, 0])
     assert len(env.engines) == 3 and all(e.time_limit_truncates for e in env.engines)
     seen = {"term": 0, "trunc": 0}
     rng = np.random.default_rng(9)
@@ -356,7 +352,7 @@ def test_emulated_sharded_env_concatenates_the_flags():
 
 @pytest.mark.timeout(1500)
 def test_emulated_off_switch_and_table():
-    lib, B = _emu(), 16
+    lib, B = emu_library(), 16
     kw = lockstep.oracle_kwargs("rware-small-4ag-v1", max_steps=6)
     off = rware_amd.WarehouseVecEnv(B, library=lib, **kw)
     on = rware_amd.WarehouseVecEnv(B, library=lib, time_limit_truncates=True, **kw)

@@ -17,20 +17,16 @@ import pytest
 
 import collision_scenarios as cs
 import golden_util as gu
-import test_global_image as gi
-import test_reset_device as rd
+import pins
 import wide_fixtures as wf
+from device_backends import BACKENDS, Gpu
 from engine_backend import EngineBackend
-from test_action_mask import mask_model
-from test_collision_structures import check_state
-from test_collision_structures import inject as inject_scenarios
-from test_episode_stats import EpisodeModel, same_buffers
+from models import PLAIN, EpisodeModel, mask_model, same_buffers, same_everything
 
 import rware_amd
 from rware_amd import _capi
 from rware_amd.vector_env import global_image_from_state
 
-BACKENDS = rd.BACKENDS                      # Host (emulated) / Gpu: .library(), .ptr(array) -> "device" pointer
 GEOMS = [(4, 256), (4, 64)]                 # one env per wavefront / one wavefront walks all four envs
 GEOM_IDS = ["e4t256", "e4t64"]
 MODES = ["next_step", "same_step", "disabled"]
@@ -40,7 +36,7 @@ OPT_IN = dict(stats=True, episode_stats=True, action_mask=True, time_limit_trunc
 
 
 def is_gpu(backend):
-    return backend is rd.Gpu
+    return backend is Gpu
 
 
 def steps_of(backend, meta):
@@ -131,7 +127,7 @@ def test_generic_kernel_replays_the_references_trace(name, geom, backend):
         assert gu.replay(be, meta, z, steps=steps_of(backend, meta)) > meta["kwargs"]["max_steps"]
         if name == "small-127ag-twostage":   # behind the last step: the critic's image, built on the device from the kernels' own state
             st = be.env.get_state()
-            for layers in (gi.PLAIN, [1, 2]):
+            for layers in (PLAIN, [1, 2]):
                 got = be.env.global_image_device(layers)
                 same(got, global_image_from_state(st, be.env.goals, layers), ("global image", layers))
     finally:
@@ -144,26 +140,10 @@ def test_constructed_states_step_like_the_reference(geom, backend):
     """the nine scenarios as one batch (ragged: 4 + 4 + 1), four steps one by one, then the same four as one fused rollout"""
     z = wf.load_straddle()
     idx = np.arange(z["meta"]["n"])
-    T = cs.T_STEPS
     for fused in (False, True):
-        env = make_env(backend, z["meta"]["kwargs"], len(idx), geom, autoreset_mode="disabled", jit="off")
-        try:
-            same(inject_scenarios(env, z, idx), z["obs"][:, 0], "the observation of the injected state")
-            if fused:
-                obs, rew, term = env.rollout(z["actions"][idx].astype(np.int32).transpose(1, 0, 2))
-                for t in range(T):
-                    same(obs[t], z["obs"][:, t + 1], ("fused observation", t))
-                    same(np.round(rew[t] * 2), z["r_rewards_x2"][:, t], ("fused reward", t))
-                    same(term[t], z["r_done"][:, t].astype(bool), ("fused done", t))
-                check_state(wf.STRADDLE, z, idx, T - 1, env.get_state(), env.shelf_xy(), rew[T - 1], term[T - 1], "fused: ")
-            else:
-                for t in range(T):
-                    obs, rew, term, _, _ = env.step(z["actions"][idx, t].astype(np.int32))
-                    check_state(wf.STRADDLE, z, idx, t, env.get_state(), env.shelf_xy(), rew, term)
-                    same(obs, z["obs"][:, t + 1], ("observation", t))
-                    same(env.get_state()["rng"], z["r_rng"][:, t], ("rng", t))
-        finally:
-            env.close()
+        pins.engine_run(wf.STRADDLE, z, idx, fused, "fused: " if fused else "", z["meta"]["kwargs"], pins.fixture_outputs(z, idx),
+                        fields=pins.AGENT_FIELDS + ("shelf_xy", "queue", "rng"), name_of=cs.name_of, library=backend.library(),
+                        envs_per_workgroup=geom[0], threads_per_workgroup=geom[1], jit="off")
 
 
 # ------------------------------------------------------------------------------------------------ fused rollouts
@@ -298,10 +278,10 @@ def test_snapshot_restore_and_masked_resets_from_host_and_device(backend):
         mask = (np.arange(B) % 3 != 1).astype(np.uint8)
         a.reset(seed=seeds, mask=mask.astype(bool))
         b.engines[0].reset_device(be.ptr(seeds), be.ptr(mask))
-        rd.same_everything(a, b, "behind the masked resets")
+        same_everything(a, b, "behind the masked resets")
         for t in range(8, 13):
             a.step(acts[t]); b.step(acts[t])
-        rd.same_everything(a, b, "five steps on")
+        same_everything(a, b, "five steps on")
     finally:
         a.close(); b.close()
 

@@ -2,10 +2,11 @@
 tests/golden/wide/generate_wide.py): loading them in the form golden_util.replay takes, and the one question both the generator and
 the tests ask of a trace — does a committed chain of movers cross agent index 64, the boundary between the two agents a lane of the
 step kernel's wavefront owns.  Plain numpy; used on the CPU and on the GPU box alike (no reference, no oracle)."""
-import json
 import os
 
 import numpy as np
+
+import pins
 
 WIDE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wide")
 TRACES = ("tiny-65ag", "small-127ag-twostage", "medium-96ag-msg1-global-inact", "imgdict-medium-100ag-sr2")
@@ -42,37 +43,31 @@ def unpack_obs(z, prefix, obs_shape):
     return flat.astype(np.float32).reshape(flat.shape[:-1] + tuple(obs_shape))
 
 
-_cache = {}
+def unpack_trace_obs(z):
+    """load_npz's `prepare` of a random trace: obs0 / obs (/ features0 / features) unpacked to float32, the packed arrays dropped"""
+    z["obs0"] = unpack_obs(z, "init_", z["meta"]["obs_shape"])
+    z["obs"] = unpack_obs(z, "", z["meta"]["obs_shape"])
+    for k in ("features0", "features"):
+        if k in z:
+            z[k] = z[k].astype(np.float32)
+    for k in [k for k in z if k.endswith(("obs_xy", "obs_bits", "img_bits", "img_u8"))]:
+        del z[k]
 
 
 def load_trace(name):
-    """(meta, fields) of a random trace, fields as golden_util.replay reads them: obs0 / obs (/ features0 / features) unpacked to float32"""
-    if name not in _cache:
-        z = dict(np.load(os.path.join(WIDE_DIR, name + ".npz"), allow_pickle=False))
-        meta = json.loads(str(z.pop("meta")))
-        z["obs0"] = unpack_obs(z, "init_", meta["obs_shape"])
-        z["obs"] = unpack_obs(z, "", meta["obs_shape"])
-        for k in ("features0", "features"):
-            if k in z:
-                z[k] = z[k].astype(np.float32)
-        for k in [k for k in z if k.endswith(("obs_xy", "obs_bits", "img_bits", "img_u8"))]:
-            del z[k]
-        for a in z.values():
-            a.setflags(write=False)
-        _cache[name] = (meta, z)
-    return _cache[name]
+    """(meta, fields) of a random trace, fields as golden_util.replay reads them (`meta` once more among them)"""
+    z = pins.load_npz(WIDE_DIR, name, prepare=unpack_trace_obs)
+    return z["meta"], z
+
+
+def unpack_scenario_obs(z):
+    """load_npz's `prepare` of a constructed fixture that stores its observations (no oracle beyond 64 agents)"""
+    if "obs_bits" in z:
+        z["obs"] = unpack_obs(z, "", z["meta"]["obs_shape"])   # (n, 1 + T, N, L): the injected state, then every step
 
 
 def load_straddle():
-    if STRADDLE not in _cache:
-        z = dict(np.load(os.path.join(WIDE_DIR, STRADDLE + ".npz"), allow_pickle=False))
-        z["meta"] = json.loads(str(z["meta"]))
-        z["obs"] = unpack_obs(z, "", z["meta"]["obs_shape"])   # (n, 1 + T, N, L): the injected state, then every step
-        for k, a in z.items():
-            if k != "meta":
-                a.setflags(write=False)
-        _cache[STRADDLE] = z
-    return _cache[STRADDLE]
+    return pins.load_npz(WIDE_DIR, STRADDLE, prepare=unpack_scenario_obs)
 
 
 def straddling_chains(x0, y0, x1, y1, W):
