@@ -49,7 +49,10 @@ extern "C" {
  * Still 4, a compatible addition: rw_config.n_agents takes 1..127 (was 1..64).  65 .. 127 agents always run the generic kernel
  * (rw_info.build_kind 0, no run-time build, not even with RW_JIT_FORCE; rw_jit_log says so), by default on workgroups of 4 envs, and
  * envs_per_workgroup * n_agents must stay below 2355 there.  128 and more stay RW_ERR_INVALID_ARG: the kernels' per-cell agent layer
- * holds id | 0x80 (loaded) in one byte.  No struct, flag, buffer kind or entry point changes. */
+ * holds id | 0x80 (loaded) in one byte.  No struct, flag, buffer kind or entry point changes.
+ * Still 4, a compatible addition: one entry point, rw_snapshot_restore_indexed (single envs restored or cloned from a snapshot by a
+ * DEVICE index array, enqueue only) with its own flag word rw_restore_flags, both declared in rware_hip_restore.h; no struct, stream flag or buffer kind changes
+ * (RW_BUF_KIND_COUNT stays 29), rw_snapshot_restore itself is unchanged. */
 #define RW_ABI_VERSION 4
 
 typedef struct rw_engine rw_engine;
@@ -516,6 +519,10 @@ int rw_snapshot_create(rw_engine *eng, rw_snapshot **out);
 int rw_snapshot_save(rw_engine *eng, rw_snapshot *snap);
 int rw_snapshot_restore(rw_engine *eng, const rw_snapshot *snap);
 int rw_snapshot_destroy(rw_engine *eng, rw_snapshot *snap);
+
+/* -- restore or clone single envs from a snapshot, by index, on the device: rw_snapshot_restore_indexed ----------------------- */
+/* (declared in a header of its own, which this one pulls in: a caller includes rware_hip.h and has it) */
+#include "rware_hip_restore.h"
 
 /* -- introspection ---------------------------------------------------------------------- */
 typedef struct rw_info {

@@ -88,6 +88,13 @@ EXPERIMENTS = {
                          extras=[(f"global image: {e.replace('rware-', '').replace('-v1', '')}, {B} envs", dict(fn="image", env_id=e, envs=B))
                                  for e, B in ((SMALL4, 16384), (SMALL4, 262144), (LARGE16, 16384))]),
 }
+# Experiments added since the seven above, in a table of their own; the command line takes the names of both
+MORE_EXPERIMENTS = {
+    # what the indexed restore costs and saves (rw_snapshot_restore_indexed), and that the per-step time did not move
+    "restore_indexed": dict(configs=THREE, legs=PARENT_OWN_PARENT, compare=[("b", ("a", "a2"))], reps=5,
+                            extras=[(f"indexed restore: {e.replace('rware-', '').replace('-v1', '')}, {B} envs", dict(fn="restore", env_id=e, envs=B))
+                                    for e, B in ((SMALL4, 16384), (SMALL4, 262144), (LARGE16, 16384))]),
+}
 NEEDS = {"step": ("rw_step_tape_device", "rw_step_tape_device_timed"), "rollout": ("rw_step_many_device", "rw_event_record"),
          "step+unpack": ("rw_step_tape_device", "rw_step_device", "rw_unpack_obs", "rw_get_buffer", "rw_event_record")}
 
@@ -303,14 +310,117 @@ def image_leg(spec):
     print(json.dumps(res))
 
 
-LEG_FUNCTIONS = {"step": step_leg, "reset": reset_leg, "image": image_leg}
+def restore_leg(spec):
+    """"Every second env takes the state of a random slot" on one output="torch" env, 20 random steps behind the snapshot:
+    (a) host    get_state(), a numpy fancy index, set_state() — the only way without the entry point; host wall time, call to the return of
+                env.sync().
+    (b) device  env.restore(token, index=<int32 CUDA tensor>): host wall time from the call to the return of env.sync() behind it, and to the
+                return of the call itself (the enqueue).  (a) and (b) are warmed, then alternate `reps` times.
+    (c) kernel  with the identity index, 50 calls each captured into one HIP graph on a stream of the env's own and replayed five times
+                between two events (us per call, median of the five): restore_indexed (gather + observation launch), refresh_obs (the
+                observation launch alone), snapshot(into=token) (rw_snapshot_save: the device-to-device copies of the same bytes and
+                nothing else).  The gather alone is the first minus the second."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import rware_amd
+
+    B, kw = spec["envs"], rware_amd.env_kwargs(spec["env_id"])
+    env = rware_amd.WarehouseVecEnv(B, output="torch", **kw)
+    eng = env.engines[0]
+    rng = np.random.default_rng(0)
+    play = lambda n: [env.step(torch.from_numpy(rng.choice(5, size=(B, env.n_agents), p=[.1, .5, .15, .15, .1]).astype(np.int32)).cuda()) for _ in range(n)]
+    env.reset(seed=1)
+    play(20)
+    token = env.snapshot()
+    saved = env.get_state()
+    play(20)
+    env.sync()
+    index = np.where(np.arange(B) % 2 == 0, rng.integers(0, B, size=B), -1).astype(np.int32)
+    hit, src = index >= 0, index[index >= 0]
+    index_t = torch.from_numpy(index).cuda()
+    torch.cuda.synchronize()
+
+    def host():
+        t0 = time.perf_counter()
+        st = env.get_state()
+        for k in st:
+            st[k][hit] = saved[k][src]
+        env.set_state(**st)
+        env.sync()
+        return time.perf_counter() - t0, None
+
+    def device():
+        t0 = time.perf_counter()
+        env.restore(token, index=index_t)
+        t1 = time.perf_counter()
+        env.sync()
+        return time.perf_counter() - t0, t1 - t0
+
+    for _ in range(2):
+        host(), device()
+    out = {"host": [], "device": [], "device_enq": []}
+    for _ in range(spec["reps"] if B <= 65536 else max(5, spec["reps"] // 5)):   # (the host form takes seconds at 262144 envs)
+        out["host"].append(host()[0])
+        total, enq = device()
+        out["device"].append(total)
+        out["device_enq"].append(enq)
+    want = env.get_state()                       # the host form and the device form have to leave the same state
+    play(3)
+    env.restore(token, index=index_t)
+    env.sync()
+    got = env.get_state()
+    assert all(np.array_equal(got[k][hit], want[k][hit]) for k in want)
+    res = {k: [1e6 * x for x in v] for k, v in out.items()}
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    eng.set_stream(s.cuda_stream)
+    ident = torch.arange(B, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    n = 50
+    calls = {"indexed": lambda: eng.restore_indexed(token[0], ident.data_ptr()), "obs": eng.refresh_obs, "copies": lambda: eng.snapshot(into=token[0]),
+             "restore": lambda: eng.restore(token[0])}
+    for key, call in calls.items():
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(s):
+            s.synchronize()
+            with torch.cuda.graph(g, stream=s):
+                for _ in range(n):
+                    call()
+            g.replay()
+            s.synchronize()
+            times = []
+            for _ in range(5):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(s)
+                g.replay()
+                e1.record(s)
+                s.synchronize()
+                times.append(1e3 * e0.elapsed_time(e1) / n)
+        res[key + "_us"] = statistics.median(times)
+    res["state_bytes"] = B * (env.n_agents * 4 + 8 + 4 * eng.Q + 48 + env.n_agents * 4 + eng.H * eng.W * (2 if eng.S > 255 else 1))
+    env.free_snapshot(token)
+    env.close()
+    print(json.dumps(res))
+
+
+LEG_FUNCTIONS = {"step": step_leg, "reset": reset_leg, "image": image_leg, "restore": restore_leg}
 med = statistics.median
 spread = lambda v: (max(v) - min(v)) / med(v)
 cell = lambda v: f"{med(v):.1f} ({100 * spread(v):.0f} %)"
 
 
 def extra_line(fn, r):
-    """One report line of a reset / image leg: us, median ((max - min) / median)."""
+    """One report line of a reset / image / restore leg: us, median ((max - min) / median)."""
+    if fn == "restore":
+        gather = r["indexed_us"] - r["obs_us"]
+        return (f"host get_state() + numpy index + set_state() {cell(r['host'])} | device restore(token, index=tensor), call to sync() {cell(r['device'])}, "
+                f"call alone {cell(r['device_enq'])} | host / device {med(r['host']) / med(r['device']):.0f} | identity index, replayed from a graph: "
+                f"gather + observation launch {r['indexed_us']:.1f} us, observation launch alone {r['obs_us']:.1f} us, gather alone (the difference) "
+                f"{gather:.1f} us ({r['state_bytes'] / 1e6:.1f} MB: {2 * r['state_bytes'] / max(gather, 1e-3) / 1e3:.0f} GB/s read + written) | the same "
+                f"bytes as device-to-device copies (rw_snapshot_save) {r['copies_us']:.1f} us, rw_snapshot_restore (copies + observation launch) "
+                f"{r['restore_us']:.1f} us | gather / copies {gather / r['copies_us']:.2f}")
     if fn == "reset":
         return (f"host reset(seed=array, mask=array) {cell(r['host'])} | device reset(seed=tensor, mask=tensor) {cell(r['device'])} | device, enqueue alone "
                 f"{cell(r['device_enqueue'])} | host / device {med(r['host']) / med(r['device']):.1f}")
@@ -344,7 +454,7 @@ def child(spec):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("experiment", nargs="?", choices=sorted(EXPERIMENTS))
+    ap.add_argument("experiment", nargs="?", choices=sorted({**EXPERIMENTS, **MORE_EXPERIMENTS}))
     ap.add_argument("--leg", help="(internal) run one leg, a JSON spec, in this process")
     ap.add_argument("--parent-lib")
     ap.add_argument("--own-lib", default=OWN_LIBRARY)
@@ -360,7 +470,7 @@ def main():
         return LEG_FUNCTIONS[spec.get("fn", "step")](spec)
     if not args.experiment or not args.parent_lib:
         ap.error("an experiment and --parent-lib are required")
-    exp = EXPERIMENTS[args.experiment]
+    exp = {**EXPERIMENTS, **MORE_EXPERIMENTS}[args.experiment]
     libs = {"parent": args.parent_lib, "own": args.own_lib}
     reps, drop = args.reps or exp["reps"], 1 if exp.get("drop_first") else 0
     wanted = lambda name: not args.only or any(o in name for o in args.only)

@@ -184,6 +184,12 @@ PROTOTYPES = {
     "rw_abi_version": (C.c_int, ()),
 }
 EXPORTS = tuple(PROTOTYPES)
+# The entry points of include/rware_hip_restore.h (which rware_hip.h includes), described the same way; tests/test_restore_header.py
+# compares them with that header.  load() declares both tables.
+RESTORE_PROTOTYPES = {
+    "rw_snapshot_restore_indexed": (C.c_int, (_vp, _vp, _vp, _i32)),
+}
+RESTORE_KEEP_RNG = 1   # enum rw_restore_flags: RW_RESTORE_KEEP_RNG
 
 
 def declare(lib, names=None):
@@ -191,7 +197,7 @@ def declare(lib, names=None):
     library may be older than this description.  No ABI check: that is load()'s."""
     missing = []
     for name in PROTOTYPES if names is None else names:
-        restype, argtypes = PROTOTYPES[name]
+        restype, argtypes = PROTOTYPES[name] if name in PROTOTYPES else RESTORE_PROTOTYPES[name]
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -237,7 +243,7 @@ def load(path: str | None = None):
             "g.build()'` (or `make -C robotic-warehouse_amd/csrc`). There is no CPU fallback.")
     _preload_hip_runtime()
     lib = C.CDLL(path)
-    for name in declare(lib):  # (this tree's own library has every entry point: what ctypes itself says of a missing one)
+    for name in declare(lib) + declare(lib, RESTORE_PROTOTYPES):  # (this tree's own library has every entry point: what ctypes itself says of a missing one)
         raise AttributeError(f"{path}: undefined symbol: {name}")
     if lib.rw_abi_version() != RW_ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.rw_abi_version()} != {RW_ABI_VERSION}")
@@ -282,6 +288,7 @@ class Engine:
         self.lib = load(library)
         self._h = C.c_void_p()
         self._arena, self.arena_allocations = {}, 0  # rollout_host's device tapes (grow-only; freed in close())
+        self._index_buf = None  # restore_indexed's device copy of a host index array (upload_index; freed in close())
         cfg = make_config(
             num_envs=num_envs, layout=layout, n_agents=n_agents, sensor_range=sensor_range, request_queue_size=request_queue_size,
             max_inactivity_steps=max_inactivity_steps, max_steps=max_steps, reward_type=reward_type,
@@ -329,6 +336,9 @@ class Engine:
             for p, _ in self._arena.values():
                 self.lib.rw_device_free(self._h, p)
             self._arena = {}
+            if self._index_buf is not None:
+                self.lib.rw_device_free(self._h, self._index_buf)
+                self._index_buf = None
             self.lib.rw_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -422,17 +432,36 @@ class Engine:
         """Copies the front of arena buffer `name` into the contiguous `host_array` (waits for the engine's stream)."""
         self._check(self.lib.rw_copy_to_host(self._h, host_array.ctypes.data, self._arena[name][0], host_array.nbytes))
 
+    def create_snapshot(self):
+        """An empty snapshot of this engine's size (rw_snapshot_create): a handle for snapshot(into=...)."""
+        h = C.c_void_p()
+        self._check(self.lib.rw_snapshot_create(self._h, C.byref(h)))
+        return h
+
     def snapshot(self, into=None):
         """Device-resident copy of the whole env state (see rw_snapshot_*); returns an opaque handle."""
-        h = into
-        if h is None:
-            h = C.c_void_p()
-            self._check(self.lib.rw_snapshot_create(self._h, C.byref(h)))
+        h = self.create_snapshot() if into is None else into
         self._check(self.lib.rw_snapshot_save(self._h, h))
         return h
 
     def restore(self, handle):
         self._check(self.lib.rw_snapshot_restore(self._h, handle))
+
+    def restore_indexed(self, handle, index_ptr, keep_rng=False):
+        """rw_snapshot_restore_indexed: env e takes the state snapshot `handle` holds for env index[e] (-1: keeps its own) — `index_ptr`
+        a DEVICE int32 [B] array; `keep_rng`: RW_RESTORE_KEEP_RNG, every env's RNG stream stays as it is.  Enqueue only (no
+        synchronisation, no host read: legal inside a stream capture); an index outside -1 .. B-1 shows at the next sync()."""
+        self._check(self.lib.rw_snapshot_restore_indexed(self._h, handle, C.c_void_p(int(index_ptr or 0)), RESTORE_KEEP_RNG if keep_rng else 0))
+
+    def upload_index(self, index):
+        """A host int32 (B,) index array copied into the device buffer this engine keeps for it (allocated once) -> its device pointer."""
+        a = np.ascontiguousarray(index, dtype=np.int32).reshape(self.B)
+        if self._index_buf is None:
+            p = C.c_void_p()
+            self._check(self.lib.rw_device_malloc(self._h, a.nbytes, C.byref(p)))
+            self._index_buf = p
+        self._check(self.lib.rw_copy_to_device(self._h, self._index_buf, a.ctypes.data, a.nbytes))
+        return self._index_buf.value
 
     def free_snapshot(self, handle):
         self._check(self.lib.rw_snapshot_destroy(self._h, handle))

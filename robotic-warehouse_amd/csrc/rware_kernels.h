@@ -120,7 +120,9 @@ enum : int { REW_GLOBAL = 0, REW_INDIVIDUAL = 1, REW_TWO_STAGE = 2 };
 enum : int { AR_DISABLED = 0, AR_NEXT_STEP = 1, AR_SAME_STEP = 2 };
 enum : int { STATUS_INVALID_ACTION = 1,
              // an AGENT_DIRECTION / AGENT_LOAD image layer of the reference would have raised IndexError (:552, :558)
-             STATUS_IMAGE_INDEX = 2 };
+             STATUS_IMAGE_INDEX = 2,
+             // rw_snapshot_restore_indexed met an index outside -1 .. B-1 (that env kept its state)
+             STATUS_RESTORE_INDEX = 4 };
 enum : int { MAX_GOALS = 16, MAX_IMAGE_LAYERS = 8 };
 enum : int { OBS_FLATTENED = 0, OBS_IMAGE = 1, OBS_FLATTENED_MSG = 2, OBS_IMAGE_MSG = 3 };  // _MSG: msg_bits > 0
 // ImageLayer values of the reference (rware/warehouse.py:59-70); 3 and 4 are written with transposed indices there (:552, :558) and

@@ -293,6 +293,8 @@ class WarehouseVecEnv(_VectorEnvBase):
         self._tviews = {}
         self._global_images = {}  # global_image_device (output="torch"): (layers, shape, dtype) -> the tensors it allocated, one per device
         self._live_actions = None
+        self._clone_token = None  # clone_envs' snapshot: allocated on first use, freed in close()
+        self._live_index = None
         self._pool = None
         self._multi = None
         # step()'s fast path: (tensor type, dtype, shape, device, bound C function, engine handle, cached result tuple); only for
@@ -663,6 +665,7 @@ class WarehouseVecEnv(_VectorEnvBase):
         v = self._torch_views()
         obs = self._obs_of(v)
         keep = []
+        self._alloc_clone_token()  # (a policy may call clone_envs: its snapshot cannot be allocated while the stream is being captured)
         with t.cuda.stream(s):
             for _ in range(max(0, int(warmup))):
                 policy(obs, v["rewards"], v["terminated_bool"])
@@ -680,10 +683,83 @@ class WarehouseVecEnv(_VectorEnvBase):
         Returns an opaque token for restore(); free it with free_snapshot()."""
         return [eng.snapshot() for eng in self.engines]
 
-    def restore(self, token):
-        """Roll every env back to a snapshot(); the engine then continues bit-identically."""
-        for eng, h in zip(self.engines, token):
-            eng.restore(h)
+    def restore(self, token, index=None, keep_rng=False):
+        """Roll every env back to a snapshot(); the engine then continues bit-identically.
+
+        `index` (B,): env e takes the state the snapshot holds for env index[e]; -1 keeps env e as it is; repeats are allowed (all
+        zeros broadcasts slot 0 to every env).  The copy is a kernel on the env's stream (rw_snapshot_restore_indexed) followed by the
+        observation launch: the call only enqueues.  Two forms:
+          - a CUDA int32 tensor (B,) on the env's device (output="torch"): zero-copy, nothing waits — legal behind a policy and inside
+            capture_loop; int64 is converted with .to(torch.int32); a multi-device env takes a list of one SHARD-LOCAL tensor per
+            device.  A value outside -1 .. B-1 leaves that env untouched and raises at the next sync();
+          - a host integer array of GLOBAL env indices (any output mode): checked here (ValueError for a value outside -1 .. B-1 and
+            for a source on another shard than its destination), made shard-local and uploaded into a buffer each engine keeps.
+        `keep_rng`: every env's RNG stream stays as it is, so clones of one state draw different request replacements; without it
+        clones are identical and stay so under identical actions.  rewards / terminated / truncated are outputs of a step and are
+        left as they are.  Returns the observations, as restore(token) does."""
+        if index is None:
+            if keep_rng:
+                raise ValueError("keep_rng applies to an indexed restore: pass index=")
+            for eng, h in zip(self.engines, token):
+                eng.restore(h)
+            return self._observations()
+        ptrs, keep = self._restore_index(index)
+        for eng, h, p in zip(self.engines, token, ptrs):
+            eng.restore_indexed(h, p, keep_rng)
+        self._live_index = keep  # alive until the next indexed restore replaces them (stream-ordered allocator: see step_async)
+        return self._observations()
+
+    def _restore_index(self, index):
+        """restore()'s index, checked -> (one device pointer per shard, what has to stay alive).  Nothing here waits for the device
+        when the index is a tensor."""
+        t, n = self._torch, len(self.engines)
+        tensors = _is_tensor_arg(index)
+        if tensors:
+            if t is None:
+                raise ValueError('a tensor index needs output="torch": only such an env enqueues on the stream the tensor is ordered on')
+            parts = list(index) if isinstance(index, (list, tuple)) else [index]
+            if len(parts) != n:
+                raise ValueError(f"expected {n} per-device index tensors (shard-local indices), got {len(parts)}")
+            out = []
+            for d, (v, (lo, hi)) in enumerate(zip(parts, self._bounds)):
+                if not v.is_cuda or v.device.index != self.devices[d]:
+                    raise ValueError(f"the index tensor of shard {d} must live on cuda:{self.devices[d]}")
+                if tuple(v.shape) != (hi - lo,):
+                    raise ValueError(f"the index tensor of shard {d} must have shape ({hi - lo},), got {tuple(v.shape)}")
+                if v.dtype not in (t.int32, t.int64):
+                    raise ValueError(f"the index tensor must be int32 or int64, got {v.dtype}")
+                out.append(v.to(t.int32).contiguous())
+            return [v.data_ptr() for v in out], out
+        h = np.asarray(index)
+        if h.dtype.kind not in "iu" or h.shape != (self.num_envs,):
+            raise ValueError(f"index must be an integer array of shape ({self.num_envs},), got {h.dtype} {h.shape}")
+        h = h.astype(np.int64)
+        if ((h < -1) | (h >= self.num_envs)).any():
+            raise ValueError(f"index values must lie in -1 .. {self.num_envs - 1}")
+        local = []
+        for lo, hi in self._bounds:
+            part = h[lo:hi]
+            if ((part >= 0) & ((part < lo) | (part >= hi))).any():
+                raise ValueError("an env can only take a state saved on its own device: a source index on another shard (a cross-device "
+                                 "copy is not supported)")
+            local.append(np.where(part >= 0, part - lo, -1).astype(np.int32))
+        return [eng.upload_index(part) for eng, part in zip(self.engines, local)], None
+
+    def _alloc_clone_token(self):
+        if self._clone_token is None:
+            self._clone_token = [eng.create_snapshot() for eng in self.engines]
+
+    def clone_envs(self, index, keep_rng=False):
+        """Env e becomes a copy of env index[e] AS IT IS NOW (-1: stays itself): a snapshot into a token the env keeps (allocated on
+        first use, freed in close()), then restore(token, index, keep_rng).  Both halves only enqueue, so with a device tensor it
+        can be called behind a policy and inside capture_loop.  `index` and `keep_rng`: as for restore().  Returns the observations."""
+        ptrs, keep = self._restore_index(index)   # (checked before anything is enqueued)
+        self._alloc_clone_token()
+        for eng, h in zip(self.engines, self._clone_token):
+            eng.snapshot(into=h)
+        for eng, h, p in zip(self.engines, self._clone_token, ptrs):
+            eng.restore_indexed(h, p, keep_rng)
+        self._live_index = keep
         return self._observations()
 
     def free_snapshot(self, token):
@@ -1035,6 +1111,9 @@ class WarehouseVecEnv(_VectorEnvBase):
         if self._multi is not None:
             self._multi.close()
             self._multi = None
+        if self._clone_token is not None and self.engines:
+            self.free_snapshot(self._clone_token)
+        self._clone_token = self._live_index = None
         for eng in self.engines:
             eng.close()
         self.engines = []
