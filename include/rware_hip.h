@@ -52,7 +52,10 @@ extern "C" {
  * holds id | 0x80 (loaded) in one byte.  No struct, flag, buffer kind or entry point changes.
  * Still 4, a compatible addition: one entry point, rw_snapshot_restore_indexed (single envs restored or cloned from a snapshot by a
  * DEVICE index array, enqueue only) with its own flag word rw_restore_flags, both declared in rware_hip_restore.h; no struct, stream flag or buffer kind changes
- * (RW_BUF_KIND_COUNT stays 29), rw_snapshot_restore itself is unchanged. */
+ * (RW_BUF_KIND_COUNT stays 29), rw_snapshot_restore itself is unchanged.
+ * Still 4, a compatible addition: one entry point, rw_unpack_obs_gather (packed rows gathered by a DEVICE index array and unpacked into
+ * float32, float16 or bfloat16 in one launch, enqueue only) with its enums rw_unpack_elem and rw_unpack_flags, declared in
+ * rware_hip_minibatch.h; no struct, stream flag or buffer kind changes, rw_unpack_obs itself is unchanged. */
 #define RW_ABI_VERSION 4
 
 typedef struct rw_engine rw_engine;
@@ -465,6 +468,10 @@ int rw_refresh_obs(rw_engine *eng);
  * normalised_coordinates) are the engine's.  The result equals what RW_BUF_OBS would hold, bit for bit.  Any FLATTENED engine, with or
  * without RW_OBS_PACKED. */
 int rw_unpack_obs(rw_engine *eng, const uint32_t *packed_dev, float *obs_f32_dev, int64_t n_rows);
+
+/* -- gather and unpack packed minibatches on the device, into float32 / float16 / bfloat16: rw_unpack_obs_gather ---------------- */
+/* (declared in a header of its own, which this one pulls in: a caller includes rware_hip.h and has it) */
+#include "rware_hip_minibatch.h"
 
 /* Warehouse.get_global_image (:966-1040) for all B envs, from the engine's current state, into a DEVICE array of the caller's — the
  * global-state input of a centralised critic, without a host visit.

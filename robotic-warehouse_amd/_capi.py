@@ -185,11 +185,18 @@ PROTOTYPES = {
 }
 EXPORTS = tuple(PROTOTYPES)
 # The entry points of include/rware_hip_restore.h (which rware_hip.h includes), described the same way; tests/test_restore_header.py
-# compares them with that header.  load() declares both tables.
+# compares them with that header.
 RESTORE_PROTOTYPES = {
     "rw_snapshot_restore_indexed": (C.c_int, (_vp, _vp, _vp, _i32)),
 }
 RESTORE_KEEP_RNG = 1   # enum rw_restore_flags: RW_RESTORE_KEEP_RNG
+# ... and those of include/rware_hip_minibatch.h, a third table (tests/test_minibatch_header.py); load() declares all three.
+MINIBATCH_PROTOTYPES = {
+    "rw_unpack_obs_gather": (C.c_int, (_vp, _vp, C.c_int64, _i32, _vp, C.c_int64, _i32, _i32, _vp)),
+}
+UNPACK_F32, UNPACK_F16, UNPACK_BF16 = 0, 1, 2   # enum rw_unpack_elem
+UNPACK_INDEX64 = 1                              # enum rw_unpack_flags: RW_UNPACK_INDEX64
+UNPACK_ELEMS = {"float32": UNPACK_F32, "float16": UNPACK_F16, "bfloat16": UNPACK_BF16}
 
 
 def declare(lib, names=None):
@@ -197,7 +204,7 @@ def declare(lib, names=None):
     library may be older than this description.  No ABI check: that is load()'s."""
     missing = []
     for name in PROTOTYPES if names is None else names:
-        restype, argtypes = PROTOTYPES[name] if name in PROTOTYPES else RESTORE_PROTOTYPES[name]
+        restype, argtypes = next(t[name] for t in (PROTOTYPES, RESTORE_PROTOTYPES, MINIBATCH_PROTOTYPES) if name in t)
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -243,7 +250,7 @@ def load(path: str | None = None):
             "g.build()'` (or `make -C robotic-warehouse_amd/csrc`). There is no CPU fallback.")
     _preload_hip_runtime()
     lib = C.CDLL(path)
-    for name in declare(lib) + declare(lib, RESTORE_PROTOTYPES):  # (this tree's own library has every entry point: what ctypes itself says of a missing one)
+    for name in declare(lib) + declare(lib, RESTORE_PROTOTYPES) + declare(lib, MINIBATCH_PROTOTYPES):  # (this tree's own library has every entry point: what ctypes itself says of a missing one)
         raise AttributeError(f"{path}: undefined symbol: {name}")
     if lib.rw_abi_version() != RW_ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.rw_abi_version()} != {RW_ABI_VERSION}")
@@ -520,6 +527,15 @@ class Engine:
     def unpack_obs_device(self, packed_ptr, out_ptr, n_rows):
         """rw_unpack_obs: `n_rows` packed rows (device uint32 [n_rows][PW]) -> float32 [n_rows][L] at `out_ptr`, on the engine's stream."""
         self._check(self.lib.rw_unpack_obs(self._h, C.c_void_p(int(packed_ptr)), C.c_void_p(int(out_ptr)), int(n_rows)))
+
+    def unpack_gather(self, packed_ptr, n_groups, rows_per_group, index_ptr, n_index, elem, index64, out_ptr):
+        """rw_unpack_obs_gather: output group i (`rows_per_group` rows of L elements at `out_ptr`, `elem` one of UNPACK_F32 / UNPACK_F16 /
+        UNPACK_BF16) <- the unpacked rows of source group index[i] of the device array uint32 [n_groups][rows_per_group][PW] at
+        `packed_ptr`; `index_ptr` a DEVICE int32 (`index64`: int64) [n_index] array, 0 / None: the identity.  Enqueue only, one launch
+        (legal inside a stream capture); an index outside 0 .. n_groups-1 gives a group of zeros and shows at the next sync()."""
+        self._check(self.lib.rw_unpack_obs_gather(self._h, C.c_void_p(int(packed_ptr or 0)), int(n_groups), int(rows_per_group),
+                                                  C.c_void_p(int(index_ptr or 0)), int(n_index), int(elem), UNPACK_INDEX64 if index64 else 0,
+                                                  C.c_void_p(int(out_ptr or 0))))
 
     def global_image(self, layers, out_ptr, pad_to_shape=None, dtype=np.float32):
         """rw_global_image: Warehouse.get_global_image of every env, built on the device from the engine's current state into the DEVICE array

@@ -18,6 +18,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -173,6 +174,10 @@ __global__ void __launch_bounds__(256) rware_unpack_obs_kernel(const uint32_t *_
         for (int j = 0; j < n; ++j) out[f + j] = e[j];
     }
 }
+
+}  // namespace rw
+#include "rware_minibatch.h"   // rw_unpack_obs_gather's kernel (uses rw::unpack_elem above)
+namespace rw {
 
 // rw_seed_device / rw_reset_device: SeedSequence(seeds[e]) -> PCG64 state of env e, one lane per env (rw::pcg_seed_state: some sixty
 // 32-bit multiplies and two 128-bit ones; no LDS, no atomics).  Each lane reads 8 bytes of seed and one mask byte and writes its column
@@ -1768,6 +1773,65 @@ int rw_unpack_obs(rw_engine *eng, const uint32_t *packed_dev, float *obs_f32_dev
     return RW_OK;
 }
 
+int rw_unpack_obs_gather(rw_engine *eng, const uint32_t *packed_dev, int64_t n_groups, int32_t rows_per_group, const void *index_dev,
+                         int64_t n_index, int32_t elem, int32_t flags, void *out_dev) {
+    // One launch of rware_unpack_gather_kernel on the engine's stream and nothing else: the host never reads the index array, so the call
+    // is legal inside a stream capture and is replayed with the graph.
+    if (!eng) return RW_ERR_INVALID_ARG;
+    if (eng->image)  // (RW_OBS_IMAGE_U8 included)
+        return fail(eng, RW_ERR_UNSUPPORTED, "rw_unpack_obs_gather: packed rows exist for FLATTENED observations only");
+    if (!packed_dev || !out_dev) return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: NULL %s", !packed_dev ? "packed_dev" : "out_dev");
+    if (n_groups < 0 || n_index < 0 || rows_per_group < 1)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: n_groups %lld, n_index %lld, rows_per_group %d", (long long)n_groups,
+                    (long long)n_index, (int)rows_per_group);
+    if (elem != RW_UNPACK_F32 && elem != RW_UNPACK_F16 && elem != RW_UNPACK_BF16)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: unknown element type %d", (int)elem);
+    if (flags & ~(int32_t)RW_UNPACK_INDEX64)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: unknown flag bits 0x%x", (unsigned)(flags & ~(int32_t)RW_UNPACK_INDEX64));
+    if (!index_dev && n_index != n_groups)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: without an index n_index (%lld) has to be n_groups (%lld)", (long long)n_index,
+                    (long long)n_groups);
+    const int index64 = (flags & RW_UNPACK_INDEX64) ? 1 : 0;
+    const unsigned elem_bytes = elem == RW_UNPACK_F32 ? 4u : 2u;
+    if ((reinterpret_cast<uintptr_t>(packed_dev) & 3u) || (reinterpret_cast<uintptr_t>(index_dev) & (index64 ? 7u : 3u)) ||
+        (reinterpret_cast<uintptr_t>(out_dev) & (elem_bytes - 1u)))
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: packed_dev has to be 4-byte aligned, index_dev and out_dev to their elements");
+    // one thread per 16 bytes of output, 256 a workgroup, at most 2^31 - 1 workgroups; the source rows are addressed in size_t words
+    const uint64_t per_group = (uint64_t)rows_per_group * (uint64_t)eng->L, chunk = 16u / elem_bytes;
+    const uint64_t max_elems = (uint64_t)0x7fffffffu * 256u * chunk;
+    if ((uint64_t)n_index > max_elems / per_group || (uint64_t)n_groups > ((uint64_t)1 << 52) / ((uint64_t)rows_per_group * (uint64_t)eng->PW))
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: %lld groups of %d rows are more than one launch holds; unpack in slices",
+                    (long long)std::max(n_index, n_groups), (int)rows_per_group);
+    if (n_index == 0) return RW_OK;
+    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
+    rw::UnpackGatherArgs a{};
+    a.packed = packed_dev;
+    a.index = index_dev;
+    a.out = out_dev;
+    a.n_elems = (uint64_t)n_index * per_group;
+    a.n_groups = n_groups;
+    a.inv_L = 1.0 / (double)eng->L;
+    a.inv_G = 1.0 / (double)rows_per_group;
+    a.status = eng->d_status;
+    a.G = rows_per_group;
+    a.L = eng->L;
+    a.PW = eng->PW;
+    a.W = eng->prm.W;
+    a.H = eng->prm.H;
+    a.normalised = eng->prm.normalised;
+    a.aligned = (reinterpret_cast<uintptr_t>(out_dev) & 15u) == 0 ? 1 : 0;
+    a.index64 = index64;
+    const unsigned blocks = (unsigned)(((a.n_elems + chunk - 1) / chunk + 255) / 256);
+    auto go = [&](auto el) {
+        hipLaunchKernelGGL((rw::rware_unpack_gather_kernel<decltype(el)::value>), dim3(blocks), dim3(256), 0, eng->stream, a);
+    };
+    if (elem == RW_UNPACK_F32) go(std::integral_constant<int, rw::UNPACK_F32>());
+    else if (elem == RW_UNPACK_F16) go(std::integral_constant<int, rw::UNPACK_F16>());
+    else go(std::integral_constant<int, rw::UNPACK_BF16>());
+    RW_HIP(eng, hipGetLastError());
+    return RW_OK;
+}
+
 int rw_global_image(rw_engine *eng, const int32_t *layers, int32_t n_layers, const int32_t *pad_to_shape, int32_t elem, void *out_dev) {
     // One launch of rware_global_image_kernel on the engine's stream and nothing else: everything the kernel needs beyond the state
     // travels in its arguments, so the call is legal inside a stream capture and is replayed with the graph.
@@ -1844,7 +1908,8 @@ int rw_sync(rw_engine *eng) {
             return fail(eng, RW_ERR_INDEX, "AGENT_DIRECTION / AGENT_LOAD image layer: an agent at x >= grid height or y >= grid "
                         "width; the reference raises IndexError there (rware/warehouse.py:552,558)");
         if (st & rw::STATUS_RESTORE_INDEX)
-            return fail(eng, RW_ERR_INVALID_ARG, "rw_snapshot_restore_indexed: an index outside -1 .. num_envs - 1 (that env kept its state)");
+            return fail(eng, RW_ERR_INVALID_ARG, "an index outside its range: rw_snapshot_restore_indexed outside -1 .. num_envs - 1 (that env kept "
+                        "its state) or rw_unpack_obs_gather outside 0 .. n_groups - 1 (that output group is zeros)");
     }
     return RW_OK;
 }

@@ -294,6 +294,8 @@ class WarehouseVecEnv(_VectorEnvBase):
         self._global_images = {}  # global_image_device (output="torch"): (layers, shape, dtype) -> the tensors it allocated, one per device
         self._live_actions = None
         self._clone_token = None  # clone_envs' snapshot: allocated on first use, freed in close()
+        self._unpacked = {}  # unpack_obs_device: (device, shape, dtype) -> the tensor it allocated
+        self._live_unpack = None
         self._live_index = None
         self._pool = None
         self._multi = None
@@ -965,6 +967,67 @@ class WarehouseVecEnv(_VectorEnvBase):
         -> numpy out; a torch tensor -> a torch tensor on the same device (plain shift / and / cast ops: call it on a minibatch)."""
         return _unpack_obs(packed, self.grid_size, self.sensor_range, self.msg_bits, self.normalised_coordinates)
 
+    def unpack_obs_device(self, packed, index=None, dtype="float32", out=None):
+        """unpack_obs(packed[index]).to(dtype) in ONE kernel on the env's stream (rw_unpack_obs_gather), without the gathered copy and the
+        intermediates of the tensor-op path: the learner's half of obs_format="packed".  output="torch" only.
+        `packed`: a contiguous CUDA int32 (or uint32) tensor (G0, ..., PW) — a rollout tape reshaped to (T*B, N, PW), the live
+        "obs_packed" (B, N, PW), or plain rows (n, PW); `index`: a 1-D CUDA int32 or int64 tensor over the FIRST dimension (repeats
+        allowed; None: the whole array); `dtype`: "float32" | "float16" | "bfloat16" or the torch dtype — float32 is bit for bit what
+        obs_format="float32" returns, the 16-bit types are that value rounded to nearest even (0 and 1 are exact: only the two
+        coordinates round).  Returns a tensor (n, ..., L): `out` if given (contiguous, of that shape and dtype, on `packed`'s device), else
+        one allocated on the first call per (shape, dtype) and overwritten by later ones.  With several devices the tensor's device picks
+        the engine.  The call only enqueues — on the stream step() uses, so it is ordered with the learner like every other call and a
+        policy inside capture_loop may make it (a replay reads the index tensor's contents at replay time).  An index outside
+        0 .. G0-1 gives rows of zeros and raises at the next sync().  ValueError for a host tensor, a wrong last dimension, a
+        non-contiguous input, an `out` of the wrong shape, dtype or device."""
+        if self.observation_type in (ObservationType.IMAGE, ObservationType.IMAGE_DICT):
+            raise ValueError("packed rows exist for FLATTENED observations only")
+        if not (hasattr(packed, "is_cuda") and hasattr(packed, "data_ptr")):
+            raise ValueError("unpack_obs_device takes torch tensors (numpy rows: unpack_obs)")
+        import torch as t
+
+        names = {"float32": t.float32, "float16": t.float16, "bfloat16": t.bfloat16}
+        tdt = names.get(dtype, dtype) if isinstance(dtype, str) else dtype
+        if tdt not in names.values():
+            raise ValueError(f'dtype must be "float32", "float16" or "bfloat16" (or the torch dtype), got {dtype!r}')
+        elem = _capi.UNPACK_ELEMS[str(tdt).split(".")[-1]]
+        L, pw = obs_length(self.sensor_range, self.msg_bits), packed_words(self.sensor_range, self.msg_bits)
+        if packed.dtype not in (t.int32, getattr(t, "uint32", t.int32)):
+            raise ValueError(f"packed rows are int32 (or uint32) words, got {packed.dtype}")
+        if packed.dim() < 2 or packed.shape[-1] != pw:
+            raise ValueError(f"expected packed rows (G0, ..., {pw}), got {tuple(packed.shape)}")
+        if not packed.is_contiguous():
+            raise ValueError("`packed` must be contiguous (reshape a tape, do not slice or transpose it)")
+        g0, rows = int(packed.shape[0]), int(np.prod(packed.shape[1:-1], dtype=np.int64))
+        n = g0
+        if index is not None:
+            if not hasattr(index, "is_cuda") or index.dtype not in (t.int32, t.int64) or index.dim() != 1 or not index.is_contiguous():
+                raise ValueError("`index` must be a contiguous 1-D int32 or int64 tensor over the first dimension of `packed`")
+            if index.device != packed.device:
+                raise ValueError(f"`index` lives on {index.device}, `packed` on {packed.device}")
+            n = int(index.shape[0])
+        shape = (n,) + tuple(packed.shape[1:-1]) + (L,)
+        if out is not None and not (hasattr(out, "is_cuda") and tuple(out.shape) == shape and out.dtype == tdt and out.device == packed.device
+                                    and out.is_contiguous()):
+            raise ValueError(f"`out` must be a contiguous {tdt} tensor of shape {shape} on {packed.device}")
+        if not packed.is_cuda:
+            raise ValueError("`packed` is a host tensor: unpack_obs_device works on the device (host rows: unpack_obs)")
+        if self.output != "torch":
+            raise ValueError('unpack_obs_device needs output="torch": only such an env enqueues on the stream the tensors are ordered on')
+        if packed.device.index not in self.devices:
+            raise ValueError(f"no engine of this env runs on {packed.device}")
+        eng = self.engines[self.devices.index(packed.device.index)]
+        if out is None:
+            key = (packed.device.index, shape, tdt)
+            out = self._unpacked.get(key)
+            if out is None:
+                out = self._unpacked[key] = t.empty(shape, dtype=tdt, device=packed.device)
+        if out.numel():  # (an empty index or an empty middle dimension: nothing to write)
+            eng.unpack_gather(packed.data_ptr(), g0, rows, None if index is None else index.data_ptr(), n, elem,
+                              index is not None and index.dtype == t.int64, out.data_ptr())
+        self._live_unpack = (packed, index, out)  # (alive until the next call: the launch is only enqueued)
+        return out
+
     # ------------------------------------------------------------------------------- state
     def get_state(self) -> dict:
         """Batched SoA state: grid (B,2,H,W), agent_* (B,N), queue (B,Q), steps/inactive (B,), rng (B,6)."""
@@ -1119,6 +1182,7 @@ class WarehouseVecEnv(_VectorEnvBase):
         self.engines = []
         self._tviews = {}
         self._global_images = {}
+        self._unpacked, self._live_unpack = {}, None
         self._fast = None          # (the fast path of step() holds the raw engine handle and views of the freed slab)
         self._fast_ok = False
         self._live_actions = None
