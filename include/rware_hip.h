@@ -55,7 +55,12 @@ extern "C" {
  * (RW_BUF_KIND_COUNT stays 29), rw_snapshot_restore itself is unchanged.
  * Still 4, a compatible addition: one entry point, rw_unpack_obs_gather (packed rows gathered by a DEVICE index array and unpacked into
  * float32, float16 or bfloat16 in one launch, enqueue only) with its enums rw_unpack_elem and rw_unpack_flags, declared in
- * rware_hip_minibatch.h; no struct, stream flag or buffer kind changes, rw_unpack_obs itself is unchanged. */
+ * rware_hip_minibatch.h; no struct, stream flag or buffer kind changes, rw_unpack_obs itself is unchanged.
+ * Still 4, a compatible addition: three entry points, rw_global_record_bytes, rw_global_records (the code byte per cell that
+ * rw_global_image expands, written as one uint8 record per env, enqueue only) and rw_global_image_gather (records gathered by a DEVICE
+ * index array and expanded into float32, uint8, float16 or bfloat16 images in one launch, enqueue only) with their enums rw_global_elem,
+ * rw_global_flags and rw_global_record_flags, declared in rware_hip_global_state.h; no struct, stream flag or buffer kind changes,
+ * rw_global_image itself is unchanged. */
 #define RW_ABI_VERSION 4
 
 typedef struct rw_engine rw_engine;
@@ -495,6 +500,10 @@ int rw_unpack_obs(rw_engine *eng, const uint32_t *packed_dev, float *obs_f32_dev
  *   smaller than the image, elem other than 0 / 1, a float32 out_dev that is not 4-byte aligned, and for an image of more than 2^30
  *   elements per env ("slice it": smaller padding, or fewer layers per call). */
 int rw_global_image(rw_engine *eng, const int32_t *layers, int32_t n_layers, const int32_t *pad_to_shape, int32_t elem, void *out_dev);
+
+/* -- the global state as byte records, and minibatches of images gathered from them: rw_global_records, rw_global_image_gather --- */
+/* (declared in a header of its own, which this one pulls in: a caller includes rware_hip.h and has it) */
+#include "rware_hip_global_state.h"
 
 /* wait for everything enqueued; returns RW_ERR_INVALID_ACTION if any step since the last
  * rw_sync saw an out-of-range action (that action was executed as NOOP), else RW_OK */

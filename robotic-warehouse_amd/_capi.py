@@ -190,13 +190,24 @@ RESTORE_PROTOTYPES = {
     "rw_snapshot_restore_indexed": (C.c_int, (_vp, _vp, _vp, _i32)),
 }
 RESTORE_KEEP_RNG = 1   # enum rw_restore_flags: RW_RESTORE_KEEP_RNG
-# ... and those of include/rware_hip_minibatch.h, a third table (tests/test_minibatch_header.py); load() declares all three.
+# ... and those of include/rware_hip_minibatch.h, a third table (tests/test_minibatch_header.py).
 MINIBATCH_PROTOTYPES = {
     "rw_unpack_obs_gather": (C.c_int, (_vp, _vp, C.c_int64, _i32, _vp, C.c_int64, _i32, _i32, _vp)),
 }
 UNPACK_F32, UNPACK_F16, UNPACK_BF16 = 0, 1, 2   # enum rw_unpack_elem
 UNPACK_INDEX64 = 1                              # enum rw_unpack_flags: RW_UNPACK_INDEX64
 UNPACK_ELEMS = {"float32": UNPACK_F32, "float16": UNPACK_F16, "bfloat16": UNPACK_BF16}
+# ... and those of include/rware_hip_global_state.h, a fourth table (tests/test_global_state_header.py); load() declares all four.
+GLOBAL_STATE_PROTOTYPES = {
+    "rw_global_record_bytes": (_i32, (_vp,)),
+    "rw_global_records": (C.c_int, (_vp, _vp)),
+    "rw_global_image_gather": (C.c_int, (_vp, _vp, C.c_int64, _vp, C.c_int64, _P(_i32), _i32, _P(_i32), _i32, _i32, _vp)),
+}
+GLOBAL_F32, GLOBAL_U8, GLOBAL_F16, GLOBAL_BF16 = 0, 1, 2, 3   # enum rw_global_elem (0 and 1: rw_global_image's `elem`)
+GLOBAL_INDEX64 = 1                                            # enum rw_global_flags: RW_GLOBAL_INDEX64
+GLOBAL_RECORD_NO_MIRROR, GLOBAL_RECORD_LOADED_NO_MIRROR = 1, 2   # enum rw_global_record_flags: byte H*W of a record
+GLOBAL_ELEMS = {"float32": GLOBAL_F32, "uint8": GLOBAL_U8, "float16": GLOBAL_F16, "bfloat16": GLOBAL_BF16}
+ALL_PROTOTYPES = (PROTOTYPES, RESTORE_PROTOTYPES, MINIBATCH_PROTOTYPES, GLOBAL_STATE_PROTOTYPES)
 
 
 def declare(lib, names=None):
@@ -204,7 +215,7 @@ def declare(lib, names=None):
     library may be older than this description.  No ABI check: that is load()'s."""
     missing = []
     for name in PROTOTYPES if names is None else names:
-        restype, argtypes = next(t[name] for t in (PROTOTYPES, RESTORE_PROTOTYPES, MINIBATCH_PROTOTYPES) if name in t)
+        restype, argtypes = next(t[name] for t in ALL_PROTOTYPES if name in t)
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -250,7 +261,7 @@ def load(path: str | None = None):
             "g.build()'` (or `make -C robotic-warehouse_amd/csrc`). There is no CPU fallback.")
     _preload_hip_runtime()
     lib = C.CDLL(path)
-    for name in declare(lib) + declare(lib, RESTORE_PROTOTYPES) + declare(lib, MINIBATCH_PROTOTYPES):  # (this tree's own library has every entry point: what ctypes itself says of a missing one)
+    for name in [n for t in ALL_PROTOTYPES for n in declare(lib, t)]:  # (this tree's own library has every entry point: what ctypes itself says of a missing one)
         raise AttributeError(f"{path}: undefined symbol: {name}")
     if lib.rw_abi_version() != RW_ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.rw_abi_version()} != {RW_ABI_VERSION}")
@@ -547,6 +558,29 @@ class Engine:
         ls = (C.c_int32 * len(layers))(*[int(l) for l in layers])
         pad = None if pad_to_shape is None else (C.c_int32 * 3)(*[int(v) for v in pad_to_shape])
         self._check(self.lib.rw_global_image(self._h, ls, len(layers), pad, 0 if dt == np.float32 else 1, C.c_void_p(int(out_ptr))))
+
+    @property
+    def global_record_bytes(self) -> int:
+        """rw_global_record_bytes: RB = (H*W + 1 + 15) & ~15, the bytes of one env's global-state record."""
+        return int(self.lib.rw_global_record_bytes(self._h))
+
+    def global_records(self, out_ptr):
+        """rw_global_records: one record per env — the code byte per cell that rw_global_image expands, a flags byte, zeros — from the
+        engine's current state into the DEVICE array uint8 [B][RB] at `out_ptr` (16-byte aligned).  Enqueue only, one launch; the status
+        word is not touched."""
+        self._check(self.lib.rw_global_records(self._h, C.c_void_p(int(out_ptr or 0))))
+
+    def global_image_gather(self, records_ptr, n_records, index_ptr, n_index, layers, out_ptr, pad_to_shape=None, elem=GLOBAL_F32, index64=False):
+        """rw_global_image_gather: output image i ([C'][H'][W'] elements of `elem`, one of GLOBAL_F32 / GLOBAL_U8 / GLOBAL_F16 / GLOBAL_BF16,
+        at `out_ptr`) <- the image of record index[i] of the DEVICE array uint8 [n_records][RB] at `records_ptr`; `index_ptr` a DEVICE int32
+        (`index64`: int64) [n_index] array, 0 / None: the identity.  Layers and padding as global_image.  Enqueue only, one launch; an index
+        outside 0 .. n_records-1 gives an image of zeros and shows at the next sync(), as does a gathered record whose flags say that a
+        requested AGENT_DIRECTION / AGENT_LOAD layer had an agent without a mirrored cell (IndexError)."""
+        ls = (C.c_int32 * len(layers))(*[int(l) for l in layers])
+        pad = None if pad_to_shape is None else (C.c_int32 * 3)(*[int(v) for v in pad_to_shape])
+        self._check(self.lib.rw_global_image_gather(self._h, C.c_void_p(int(records_ptr or 0)), int(n_records), C.c_void_p(int(index_ptr or 0)),
+                                                    int(n_index), ls, len(layers), pad, int(elem), GLOBAL_INDEX64 if index64 else 0,
+                                                    C.c_void_p(int(out_ptr or 0))))
 
     def device_array(self, name, dtype=None) -> DeviceArray:
         """`dtype`: present the buffer as another dtype of the same width ("obs_packed" as int32 for torch, whose uint32 has no shift ops)."""

@@ -267,157 +267,8 @@ __global__ void __launch_bounds__(256) rware_restore_indexed_kernel(const int32_
     }
 }
 
-// rw_global_image: Warehouse.get_global_image (rware/warehouse.py:966-1040) of every env, [B][C'][H'][W'] floats or bytes, from what the
-// step kernels keep — the shelf shadow, the packed agent records, the queue — so no derived view is refreshed.  A workgroup takes
-// `E` consecutive envs and builds ONE code byte per cell in LDS,
-//     bit 0 shelf | bit 1 requested | bit 2 agent | bit 3 goal | bit 4 AGENT_LOAD | bits 5..7 AGENT_DIRECTION (dir + 1),
-// the last two on the MIRRORED cell (the reference writes `layer[ag.x, ag.y]` on an (H, W) array, :1003, :1008): an agent at x >= H or
-// y >= W writes nothing and sets STATUS_IMAGE_INDEX (the reference raises IndexError), "a later agent overwrites an earlier one" is an
-// LDS atomicMax of (agent index << 3 | dir + 1).  The output is then a GATHER: every output element looks up the code byte of the
-// cell it shows (zero in the padding) and takes its layer's bits out of it, so no store can leave the workgroup's own [e0, e0 + ne)
-// slice of `out`.  A pure store stream: 16-byte non-temporal stores on the 16-byte boundaries of the ADDRESS (`phase`: the element
-// index of `out` within its 16-byte line), single elements in front of the first and behind the last boundary of the slice.
-// No thread returns before the last barrier.
-struct GlobalImageArgs {
-    int32_t B, H, W, HW, N, Q, S, SW, n_goals;
-    int32_t E;                       // envs per workgroup
-    int32_t n_layers, Cp, Hp, Wp;    // layers asked for; the padded shape
-    int32_t c0, h0, w0;              // zero padding in front, per axis (:1029)
-    int32_t phase;                   // (address of out / element size) % (16 / element size)
-    int32_t de, dch, dy, dx;         // blockDim.x 16-byte pieces further on in [env][C'][H'][W'] — that many elements, decomposed
-    uint32_t layers;                 // 4 bits per channel: its rw_image_layer
-    uint32_t transposed;             // bit 0: AGENT_DIRECTION among the layers, bit 1: AGENT_LOAD
-};
-template <typename CellT, typename ElemT>
-__global__ void __launch_bounds__(256) rware_global_image_kernel(const CellT *__restrict__ shadow, const uint32_t *__restrict__ rec,
-                                                                  const int32_t *__restrict__ queue, const int32_t *__restrict__ goal_cells,
-                                                                  int32_t *status, ElemT *__restrict__ out, const GlobalImageArgs a) {
-    extern __shared__ __align__(16) int32_t smem[];
-    constexpr int VE = 16 / (int)sizeof(ElemT);  // elements of a 16-byte store
-    const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
-    const int e0 = (int)blockIdx.x * a.E;
-    const int ne = a.B - e0 < a.E ? a.B - e0 : a.E;  // (the last workgroup may be ragged; the launch has ceil(B / E) of them: ne >= 1)
-    const int HW = a.HW, HWQ = (HW + 3) >> 2;         // code words per env: one byte per cell
-    uint32_t *const s_lut = reinterpret_cast<uint32_t *>(smem);                 // [8]       per channel: shift | mask << 8 | xor << 16
-    uint32_t *const s_req = s_lut + 8;                                          // [E][SW]   bit s: shelf id s is in the queue
-    int *const s_mir = reinterpret_cast<int *>(s_req + a.E * a.SW);             // [E][HW]   agent index << 3 | dir + 1, on the mirrored cell
-    uint32_t *const s_codew = reinterpret_cast<uint32_t *>(s_mir + a.E * HW);   // [E][HWQ]  the code bytes, as words for the atomics
-    uint8_t *const s_code = reinterpret_cast<uint8_t *>(s_codew);
-    for (int i = tid; i < a.E * (a.SW + HW + HWQ); i += nt) s_req[i] = 0u;
-    if (tid < 8) {
-        // layer -> where its value sits in the code byte: SHELVES bit 0, REQUESTS 1, AGENTS 2, AGENT_DIRECTION bits 5..7, AGENT_LOAD 4,
-        // GOALS 3, ACCESSIBLE bit 2 inverted; a channel beyond the list (padding) reads 0 through a zero mask
-        const uint32_t l = (a.layers >> (4 * tid)) & 15u;
-        const uint32_t sh = (0x2345210u >> (4 * l)) & 15u, mask = l == (uint32_t)LAYER_AGENT_DIRECTION ? 7u : 1u;
-        s_lut[tid] = tid < a.n_layers ? sh | mask << 8 | (l == (uint32_t)LAYER_ACCESSIBLE ? 1u : 0u) << 16 : 0u;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < ne * a.Q; idx += nt) {
-        const int e = idx / a.Q, s = queue[(size_t)e0 * a.Q + idx];
-        if (s > 0 && s <= a.S) atomicOr(&s_req[e * a.SW + (s >> 5)], 1u << (s & 31));
-    }
-    for (int idx = tid; idx < ne * a.n_goals; idx += nt) {
-        const int e = idx / a.n_goals, c = goal_cells[idx - e * a.n_goals];
-        if ((unsigned)c < (unsigned)HW) atomicOr(&s_codew[e * HWQ + (c >> 2)], 8u << (8 * (c & 3)));
-    }
-    for (int idx = tid; idx < ne * a.N; idx += nt) {
-        const int e = idx / a.N, i = idx - e * a.N;
-        const uint32_t r = rec[(size_t)e0 * a.N + idx];
-        const int c = rec_cell(r);
-        if (c >= HW) continue;  // (no state the engine produces; a record written from outside could say so)
-        atomicOr(&s_codew[e * HWQ + (c >> 2)], 4u << (8 * (c & 3)));
-        if (a.transposed) {
-            const int y = c / a.W, x = c - y * a.W;
-            const bool inside = x < a.H && y < a.W;   // `layer[ag.x, ag.y]`: row x of H, column y of W
-            const int m = x * a.W + y;
-            const bool loaded = (a.transposed & 2u) && rec_carry(r) > 0;
-            if (inside) {
-                if (a.transposed & 1u) atomicMax(&s_mir[e * HW + m], i << 3 | (rec_dir(r) + 1));
-                if (loaded) atomicOr(&s_codew[e * HWQ + (m >> 2)], 16u << (8 * (m & 3)));
-            } else if ((a.transposed & 1u) || loaded) {
-                atomicOr(status, (int)STATUS_IMAGE_INDEX);
-            }
-        }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < ne * HW; idx += nt) {  // (every thread owns the bytes it rewrites)
-        const int e = idx / HW, c = idx - e * HW;
-        const uint32_t s = (uint32_t)shadow[(size_t)e0 * HW + idx];
-        uint32_t code = s_code[e * HWQ * 4 + c] | ((uint32_t)s_mir[e * HW + c] & 7u) << 5;
-        if (s) code |= 1u | (s <= (uint32_t)a.S && ((s_req[e * a.SW + (s >> 5)] >> (s & 31)) & 1u) ? 2u : 0u);
-        s_code[e * HWQ * 4 + c] = (uint8_t)code;
-    }
-    __syncthreads();
-    // the workgroup's slice of `out`: n elements from element g0 (host-checked: E * C' H' W' < 2^31)
-    const int HpWp = a.Hp * a.Wp, CHW = a.Cp * HpWp, n = ne * CHW;
-    const size_t g0 = (size_t)e0 * (size_t)CHW;
-    ElemT *const o = out + g0;
-    int head = (VE - (int)(((size_t)a.phase + g0) % VE)) % VE;  // elements in front of the slice's first 16-byte boundary
-    if (head > n) head = n;
-    const int nv = (n - head) / VE, tail = head + nv * VE;
-    struct Pos { int e, ch, y, x; };
-    auto pos_of = [&](int l) -> Pos {
-        Pos p;
-        p.e = l / CHW;
-        const int r = l - p.e * CHW;
-        p.ch = r / HpWp;
-        const int r2 = r - p.ch * HpWp;
-        p.y = r2 / a.Wp;
-        p.x = r2 - p.y * a.Wp;
-        return p;
-    };
-    auto value = [&](const Pos &p) -> uint32_t {
-        const unsigned ch = (unsigned)(p.ch - a.c0), y = (unsigned)(p.y - a.h0), x = (unsigned)(p.x - a.w0);
-        if (ch >= (unsigned)a.n_layers || y >= (unsigned)a.H || x >= (unsigned)a.W) return 0u;
-        const uint32_t t = s_lut[ch], code = s_code[p.e * HWQ * 4 + (int)(y * (unsigned)a.W + x)];
-        return ((code >> (t & 255u)) & ((t >> 8) & 255u)) ^ (t >> 16);
-    };
-    auto next = [&](Pos &p) {
-        if (++p.x == a.Wp) {
-            p.x = 0;
-            if (++p.y == a.Hp) {
-                p.y = 0;
-                if (++p.ch == a.Cp) { p.ch = 0; ++p.e; }
-            }
-        }
-    };
-    // (a thread's 16-byte pieces lie blockDim.x * VE elements apart: it decomposes the first one's index and steps on by that
-    //  distance as the host decomposed it — three integer divisions per thread instead of per piece)
-    auto advance = [&](Pos &p) {
-        p.x += a.dx; if (p.x >= a.Wp) { p.x -= a.Wp; ++p.y; }
-        p.y += a.dy; if (p.y >= a.Hp) { p.y -= a.Hp; ++p.ch; }
-        p.ch += a.dch; if (p.ch >= a.Cp) { p.ch -= a.Cp; ++p.e; }
-        p.e += a.de;
-    };
-    Pos first = pos_of(head + (tid < nv ? tid : 0) * VE);
-    for (int v = tid; v < nv; v += nt, advance(first)) {
-        const int l = head + v * VE;
-        Pos p = first;
-        if constexpr (sizeof(ElemT) == 4) {
-            float4 f;
-            f.x = (float)value(p); next(p);
-            f.y = (float)value(p); next(p);
-            f.z = (float)value(p); next(p);
-            f.w = (float)value(p);
-            store_f4_nt(reinterpret_cast<float4 *>(o + l), f);
-        } else {
-            uint32_t w[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                uint32_t acc = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { acc |= value(p) << (8 * j); next(p); }
-                w[k] = acc;
-            }
-            store_u4_nt(reinterpret_cast<u32x4 *>(o + l), u32x4{w[0], w[1], w[2], w[3]});
-        }
-    }
-    for (int k = tid; k < head + (n - tail); k += nt) {
-        const int l = k < head ? k : tail + (k - head);
-        o[l] = (ElemT)value(pos_of(l));
-    }
-}
 }  // namespace rw
+#include "rware_global_state.h"   // rw_global_image, rw_global_records, rw_global_image_gather: the kernels and their two shared halves
 
 namespace {
 
@@ -1832,6 +1683,46 @@ int rw_unpack_obs_gather(rw_engine *eng, const uint32_t *packed_dev, int64_t n_g
     return RW_OK;
 }
 
+// What rw_global_image and rw_global_image_gather share: the layer list, the padded shape and the element's alignment, checked and
+// written into `a` (layers, transposed, n_layers, the padded shape and its offsets, phase); `chw`: elements per image.
+static int global_image_plan(rw_engine *eng, const char *who, const int32_t *layers, int32_t n_layers, const int32_t *pad_to_shape,
+                             size_t esize, const void *out_dev, rw::GlobalImageArgs &a, uint64_t &chw) {
+    const rw::Params &p = eng->prm;
+    for (int l = 0; l < n_layers; ++l) {
+        const int v = layers[l];
+        if (v < RW_LAYER_SHELVES || v > RW_LAYER_ACCESSIBLE)  // (the reference: ValueError, rware/warehouse.py:1018)
+            return fail(eng, RW_ERR_INVALID_ARG, "%s: unknown image layer %d", who, v);
+        a.layers |= (uint32_t)v << (4 * l);
+        a.transposed |= v == RW_LAYER_AGENT_DIRECTION ? 1u : v == RW_LAYER_AGENT_LOAD ? 2u : 0u;
+    }
+    const int shape[3] = {n_layers, p.H, p.W};
+    int padded[3], before[3];
+    for (int k = 0; k < 3; ++k) {
+        padded[k] = pad_to_shape ? pad_to_shape[k] : shape[k];
+        if (padded[k] < shape[k])  // (the reference: AssertionError, :1028)
+            return fail(eng, RW_ERR_INVALID_ARG, "%s: pad_to_shape[%d] = %d is smaller than the image's %d", who, k, padded[k], shape[k]);
+        before[k] = (padded[k] - shape[k]) / 2;
+    }
+    chw = (uint64_t)padded[0] * (uint64_t)padded[1] * (uint64_t)padded[2];  // (three factors below 2^31: no overflow)
+    if (chw > (1ull << 30))
+        return fail(eng, RW_ERR_INVALID_ARG, "%s: %llu elements per env are more than one launch holds; slice it (smaller "
+                    "padding, or fewer layers per call)", who, (unsigned long long)chw);
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(out_dev);
+    if (addr % esize) return fail(eng, RW_ERR_INVALID_ARG, "%s: a %s out_dev has to be %d-byte aligned", who, esize == 4 ? "float32" : "16-bit", (int)esize);
+    a.H = p.H; a.W = p.W; a.HW = p.HW; a.N = p.N; a.Q = p.Q; a.S = p.S; a.SW = p.SW; a.n_goals = p.n_goals;
+    a.n_layers = n_layers; a.Cp = padded[0]; a.Hp = padded[1]; a.Wp = padded[2];
+    a.c0 = before[0]; a.h0 = before[1]; a.w0 = before[2];
+    a.phase = (int32_t)((addr / esize) % (16 / esize));
+    return RW_OK;
+}
+// ... and the distance between two 16-byte pieces of one thread, decomposed over [env][C'][H'][W']
+static void global_image_stride(rw::GlobalImageArgs &a, unsigned threads, size_t esize, uint64_t chw) {
+    const uint64_t plane = (uint64_t)a.Hp * (uint64_t)a.Wp;
+    const uint64_t stride = (uint64_t)threads * (16 / esize), in_env = stride % chw, in_plane = in_env % plane;
+    a.de = (int32_t)(stride / chw); a.dch = (int32_t)(in_env / plane);
+    a.dy = (int32_t)(in_plane / a.Wp); a.dx = (int32_t)(in_plane % a.Wp);
+}
+
 int rw_global_image(rw_engine *eng, const int32_t *layers, int32_t n_layers, const int32_t *pad_to_shape, int32_t elem, void *out_dev) {
     // One launch of rware_global_image_kernel on the engine's stream and nothing else: everything the kernel needs beyond the state
     // travels in its arguments, so the call is legal inside a stream capture and is replayed with the graph.
@@ -1841,32 +1732,10 @@ int rw_global_image(rw_engine *eng, const int32_t *layers, int32_t n_layers, con
     if (elem != 0 && elem != 1) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image: elem %d is neither 0 (float32) nor 1 (uint8)", elem);
     const rw::Params &p = eng->prm;
     rw::GlobalImageArgs a{};
-    for (int l = 0; l < n_layers; ++l) {
-        const int v = layers[l];
-        if (v < RW_LAYER_SHELVES || v > RW_LAYER_ACCESSIBLE)  // (the reference: ValueError, rware/warehouse.py:1018)
-            return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image: unknown image layer %d", v);
-        a.layers |= (uint32_t)v << (4 * l);
-        a.transposed |= v == RW_LAYER_AGENT_DIRECTION ? 1u : v == RW_LAYER_AGENT_LOAD ? 2u : 0u;
-    }
-    const int shape[3] = {n_layers, p.H, p.W};
-    int padded[3], before[3];
-    for (int k = 0; k < 3; ++k) {
-        padded[k] = pad_to_shape ? pad_to_shape[k] : shape[k];
-        if (padded[k] < shape[k])  // (the reference: AssertionError, :1028)
-            return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image: pad_to_shape[%d] = %d is smaller than the image's %d", k, padded[k], shape[k]);
-        before[k] = (padded[k] - shape[k]) / 2;
-    }
-    const uint64_t chw = (uint64_t)padded[0] * (uint64_t)padded[1] * (uint64_t)padded[2];  // (three factors below 2^31: no overflow)
-    if (chw > (1ull << 30))
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image: %llu elements per env are more than one launch holds; slice it (smaller "
-                    "padding, or fewer layers per call)", (unsigned long long)chw);
     const size_t esize = elem == 0 ? sizeof(float) : 1;
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(out_dev);
-    if (addr % esize) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image: a float32 out_dev has to be 4-byte aligned");
-    a.B = p.B; a.H = p.H; a.W = p.W; a.HW = p.HW; a.N = p.N; a.Q = p.Q; a.S = p.S; a.SW = p.SW; a.n_goals = p.n_goals;
-    a.n_layers = n_layers; a.Cp = padded[0]; a.Hp = padded[1]; a.Wp = padded[2];
-    a.c0 = before[0]; a.h0 = before[1]; a.w0 = before[2];
-    a.phase = (int32_t)((addr / esize) % (16 / esize));
+    uint64_t chw = 0;
+    if (const int rc = global_image_plan(eng, "rw_global_image", layers, n_layers, pad_to_shape, esize, out_dev, a, chw)) return rc;
+    a.B = p.B;
     // Envs per workgroup: some 8192 elements to store, within 60 KB of LDS (9 words of table, then per env: the request bitmap, a
     // word and a byte per cell — at most 51 KB at the 10000 cells rw_create admits) and within what an int indexes.
     const int words_per_env = p.SW + p.HW + (p.HW + 3) / 4;
@@ -1877,9 +1746,7 @@ int rw_global_image(rw_engine *eng, const int32_t *layers, int32_t n_layers, con
     // (a workgroup that has little to store is one wavefront: a 3-env batch does not need four)
     const unsigned threads = (uint64_t)a.E * std::max<uint64_t>(chw / (16 / esize), (uint64_t)p.HW) >= 1024 ? 256u : 64u;
     RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    const uint64_t stride = (uint64_t)threads * (16 / esize), in_env = stride % chw, in_plane = in_env % ((uint64_t)padded[1] * padded[2]);
-    a.de = (int32_t)(stride / chw); a.dch = (int32_t)(in_env / ((uint64_t)padded[1] * padded[2]));
-    a.dy = (int32_t)(in_plane / padded[2]); a.dx = (int32_t)(in_plane % padded[2]);
+    global_image_stride(a, threads, esize, chw);
     const int32_t *goal_cells = reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(eng->d_prm) + offsetof(rw::Params, goal_cells));
     auto go = [&](auto cell, auto el) {  // (`cell`: the shelf shadow's element type; `el`: the output's)
         using Cell = decltype(cell);
@@ -1889,6 +1756,102 @@ int rw_global_image(rw_engine *eng, const int32_t *layers, int32_t n_layers, con
     };
     if (eng->wide) elem == 0 ? go(uint16_t(), float()) : go(uint16_t(), uint8_t());
     else elem == 0 ? go(uint8_t(), float()) : go(uint8_t(), uint8_t());
+    RW_HIP(eng, hipGetLastError());
+    return RW_OK;
+}
+
+int32_t rw_global_record_bytes(const rw_engine *eng) {
+    if (!eng) return RW_ERR_INVALID_ARG;
+    return (eng->prm.HW + 1 + 15) & ~15;
+}
+
+int rw_global_records(rw_engine *eng, void *records_dev) {
+    // One launch of rware_global_records_kernel on the engine's stream and nothing else (as rw_global_image); the status word is
+    // neither read nor written.
+    if (!eng) return RW_ERR_INVALID_ARG;
+    if (!records_dev) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_records: NULL records_dev");
+    if (reinterpret_cast<uintptr_t>(records_dev) & 15u)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_records: records_dev has to be 16-byte aligned");
+    const rw::Params &p = eng->prm;
+    const int RB = rw_global_record_bytes(eng);
+    rw::GlobalImageArgs a{};
+    a.B = p.B; a.H = p.H; a.W = p.W; a.HW = p.HW; a.N = p.N; a.Q = p.Q; a.S = p.S; a.SW = p.SW; a.n_goals = p.n_goals;
+    // Envs per workgroup: some 4096 cells to read and as many bytes to store, within 60 KB of LDS (per env: the record, the request
+    // bitmap and a word per cell).
+    const int words_per_env = RB / 4 + p.SW + p.HW;
+    const int by_work = std::max(1, 4096 / p.HW), by_lds = (60 * 1024 / 4) / words_per_env;
+    a.E = std::max(1, std::min(std::min(p.B, 64), std::min(by_work, by_lds)));
+    const size_t lds = sizeof(int32_t) * (size_t)a.E * words_per_env;
+    const unsigned n_wg = (unsigned)((p.B + a.E - 1) / a.E);
+    const unsigned threads = (uint64_t)a.E * (uint64_t)p.HW >= 1024 ? 256u : 64u;
+    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
+    const int32_t *goal_cells = reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(eng->d_prm) + offsetof(rw::Params, goal_cells));
+    if (eng->wide)
+        hipLaunchKernelGGL((rw::rware_global_records_kernel<uint16_t>), dim3(n_wg), dim3(threads), lds, eng->stream, (const uint16_t *)eng->d_shadow,
+                           (const uint32_t *)eng->d_rec, (const int32_t *)p.queue, goal_cells, (uint8_t *)records_dev, RB, a);
+    else
+        hipLaunchKernelGGL((rw::rware_global_records_kernel<uint8_t>), dim3(n_wg), dim3(threads), lds, eng->stream, (const uint8_t *)eng->d_shadow,
+                           (const uint32_t *)eng->d_rec, (const int32_t *)p.queue, goal_cells, (uint8_t *)records_dev, RB, a);
+    RW_HIP(eng, hipGetLastError());
+    return RW_OK;
+}
+
+int rw_global_image_gather(rw_engine *eng, const uint8_t *records_dev, int64_t n_records, const void *index_dev, int64_t n_index,
+                           const int32_t *layers, int32_t n_layers, const int32_t *pad_to_shape, int32_t elem, int32_t flags, void *out_dev) {
+    // One launch of rware_global_image_gather_kernel on the engine's stream and nothing else: the host never reads the index or a record.
+    if (!eng) return RW_ERR_INVALID_ARG;
+    if (!records_dev || !layers || !out_dev)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: NULL %s", !records_dev ? "records_dev" : !layers ? "layers" : "out_dev");
+    if (n_records < 0 || n_index < 0)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: n_records %lld, n_index %lld", (long long)n_records, (long long)n_index);
+    if (!index_dev && n_index != n_records)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: without an index n_index (%lld) has to be n_records (%lld)",
+                    (long long)n_index, (long long)n_records);
+    if (elem < RW_GLOBAL_F32 || elem > RW_GLOBAL_BF16) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: unknown element type %d", (int)elem);
+    if (flags & ~(int32_t)RW_GLOBAL_INDEX64)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: unknown flag bits 0x%x", (unsigned)(flags & ~(int32_t)RW_GLOBAL_INDEX64));
+    if (n_layers < 1 || n_layers > rw::MAX_IMAGE_LAYERS)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: n_layers %d not in 1..8", n_layers);
+    const int index64 = (flags & RW_GLOBAL_INDEX64) ? 1 : 0;
+    if ((reinterpret_cast<uintptr_t>(records_dev) & 15u) || (reinterpret_cast<uintptr_t>(index_dev) & (index64 ? 7u : 3u)))
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: records_dev has to be 16-byte aligned, index_dev to its element");
+    const size_t esize = elem == RW_GLOBAL_F32 ? 4 : elem == RW_GLOBAL_U8 ? 1 : 2;
+    rw::GlobalImageArgs a{};
+    uint64_t chw = 0;
+    if (const int rc = global_image_plan(eng, "rw_global_image_gather", layers, n_layers, pad_to_shape, esize, out_dev, a, chw)) return rc;
+    const int RB = rw_global_record_bytes(eng);
+    // (image numbers are ints in the kernel; record offsets are size_t bytes)
+    if (n_index > 0x7fffffff || (uint64_t)n_records > ((uint64_t)1 << 52) / (uint64_t)RB)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: %lld images of %lld records are more than one launch holds; gather in slices",
+                    (long long)n_index, (long long)n_records);
+    if (n_index == 0) return RW_OK;
+    a.B = (int32_t)n_index;
+    // Images per workgroup: some 8192 elements to store (as rw_global_image), within 60 KB of LDS (the table, then per image its
+    // record and 8 bytes of index — at most 10 KB at the 10000 cells rw_create admits).
+    const int by_work = (int)std::max<uint64_t>(1, 8192 / chw), by_lds = (60 * 1024 - 32) / (RB + 8);
+    a.E = std::max(1, std::min((int)std::min<int64_t>(n_index, 64), std::min(by_work, by_lds)));
+    const size_t lds = 32 + (size_t)a.E * ((size_t)RB + 8);
+    const unsigned n_wg = (unsigned)((n_index + a.E - 1) / a.E);
+    // (four wavefronts once there are 16 lookups a thread — counted in ELEMENTS, whatever their size: a uint8 store has 16 lookups in
+    //  front of it, and one wavefront per workgroup left the narrow types a quarter of the float32 kernel's waves, 2048 against 8192)
+    const unsigned threads = (uint64_t)a.E * chw >= 4096 ? 256u : 64u;
+    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
+    global_image_stride(a, threads, esize, chw);
+    rw::GlobalGatherArgs g{};
+    g.records = records_dev;
+    g.index = index_dev;
+    g.n_records = n_records;
+    g.RB = RB;
+    g.index64 = index64;
+    auto go = [&](auto el) {
+        using Elem = decltype(el);
+        hipLaunchKernelGGL((rw::rware_global_image_gather_kernel<Elem>), dim3(n_wg), dim3(threads), lds, eng->stream, g, eng->d_status,
+                           (Elem *)out_dev, a);
+    };
+    if (elem == RW_GLOBAL_F32) go(float());
+    else if (elem == RW_GLOBAL_U8) go(uint8_t());
+    else if (elem == RW_GLOBAL_F16) go(rw::F16Bits());
+    else go(rw::BF16Bits());
     RW_HIP(eng, hipGetLastError());
     return RW_OK;
 }
@@ -1909,7 +1872,8 @@ int rw_sync(rw_engine *eng) {
                         "width; the reference raises IndexError there (rware/warehouse.py:552,558)");
         if (st & rw::STATUS_RESTORE_INDEX)
             return fail(eng, RW_ERR_INVALID_ARG, "an index outside its range: rw_snapshot_restore_indexed outside -1 .. num_envs - 1 (that env kept "
-                        "its state) or rw_unpack_obs_gather outside 0 .. n_groups - 1 (that output group is zeros)");
+                        "its state), rw_unpack_obs_gather outside 0 .. n_groups - 1 (that output group is zeros) or rw_global_image_gather outside "
+                        "0 .. n_records - 1 (that image is zeros)");
     }
     return RW_OK;
 }

@@ -296,6 +296,9 @@ class WarehouseVecEnv(_VectorEnvBase):
         self._clone_token = None  # clone_envs' snapshot: allocated on first use, freed in close()
         self._unpacked = {}  # unpack_obs_device: (device, shape, dtype) -> the tensor it allocated
         self._live_unpack = None
+        self._global_records = None  # global_records_device (output="torch"): the tensors it allocated, one per device
+        self._record_images = {}  # global_image_from_records: (device, shape, dtype) -> the tensor it allocated
+        self._live_global_records = self._live_record_images = None
         self._live_index = None
         self._pool = None
         self._multi = None
@@ -1170,6 +1173,119 @@ class WarehouseVecEnv(_VectorEnvBase):
             eng.read_scratch("global_image", part)
         return parts[0] if len(parts) == 1 else np.concatenate(parts, axis=0)
 
+    @property
+    def global_record_bytes(self) -> int:
+        """RB = (H*W + 1 + 15) & ~15: the bytes of one env's global-state record (global_records_device)."""
+        return self.engines[0].global_record_bytes
+
+    def global_records_device(self, out=None):
+        """The critic's global state as BYTE RECORDS (rw_global_records): uint8 (B, RB), one record per env — byte y*W + x the code of cell
+        (x, y) (bit 0 shelf, 1 requested, 2 agent, 3 goal, 4 AGENT_LOAD and 5..7 AGENT_DIRECTION on the mirrored cell), byte H*W two flags
+        (an agent / a carrying agent without a mirrored cell), zeros up to RB (include/rware_hip_global_state.h).  Every layer of
+        get_global_image at about one byte per cell: keep a (T, B, RB) tape of these instead of images and expand only the minibatches
+        the critic draws (global_image_from_records).  One kernel on the env's stream, from the state the current observation describes;
+        it never raises — whether the AGENT_DIRECTION / AGENT_LOAD layers are asked for is decided when records are gathered.
+        output="torch": a CUDA tensor allocated on the first call and overwritten by later ones — or `out`, a contiguous uint8 CUDA tensor
+        (B, RB) whose address is 16-byte aligned (a slot of a (T, B, RB) tape is).  Enqueue only: a policy inside capture_loop may call
+        it (into a preallocated `out`).  A sharded env returns one tensor per device (`out`: one per device).
+        numpy output: the same kernel into a device scratch array of the engine's, then sync(), and a host array gathered over the shards."""
+        rb = self.global_record_bytes
+        if self.output == "torch":
+            t = self._torch
+            outs = self._global_records if out is None else list(out) if isinstance(out, (list, tuple)) else [out]
+            if outs is None:
+                outs = self._global_records = [t.empty((eng.B, rb), dtype=t.uint8, device=f"cuda:{dev}") for eng, dev in zip(self.engines, self.devices)]
+            if len(outs) != len(self.engines):
+                raise ValueError(f"`out` must hold one tensor per device ({len(self.engines)})")
+            for eng, dev, o in zip(self.engines, self.devices, outs):
+                if not (hasattr(o, "is_cuda") and o.is_cuda and o.device.index == dev and o.dtype == t.uint8 and tuple(o.shape) == (eng.B, rb)
+                        and o.is_contiguous() and o.data_ptr() % 16 == 0):
+                    raise ValueError(f"`out` must be a contiguous, 16-byte aligned uint8 CUDA tensor of shape {(eng.B, rb)} on device {dev}")
+            for eng, o in zip(self.engines, outs):
+                eng.global_records(o.data_ptr())
+            self._live_global_records = outs  # (a caller's `out` stays alive until the next call: the launch is only enqueued)
+            return outs[0] if len(outs) == 1 else tuple(outs)
+        if out is not None:
+            raise ValueError('`out` is a device tensor: it exists with output="torch" only')
+        parts = [np.empty((eng.B, rb), np.uint8) for eng in self.engines]
+        for eng, part in zip(self.engines, parts):
+            eng.global_records(eng.scratch("global_records", part.nbytes).value)
+        for eng in self.engines:
+            eng.sync()
+        for eng, part in zip(self.engines, parts):
+            eng.read_scratch("global_records", part)
+        return parts[0] if len(parts) == 1 else np.concatenate(parts, axis=0)
+
+    def global_image_from_records(self, records, index=None, image_layers=(ImageLayer.SHELVES, ImageLayer.GOALS), pad_to_shape=None,
+                                  dtype="float32", out=None):
+        """global_image_device for a MINIBATCH of stored records (rw_global_image_gather): image i is the image of record index[i], layer
+        for layer what get_global_image gave for the state that record was taken from.  output="torch" only.
+        `records`: a contiguous CUDA uint8 tensor (..., RB) — a (T, B, RB) tape counts as T*B records; `index`: a 1-D CUDA int32 or int64
+        tensor over the flattened records (repeats allowed; None: all of them, in order); `dtype`: "float32" | "uint8" | "float16" |
+        "bfloat16" or the torch dtype (every value is an integer in 0 .. 4, exact in all four).  Returns a tensor (n, C', H', W'): `out`
+        if given (contiguous, of that shape and dtype, on `records`' device; any element offset will do), else one allocated on the
+        first call per (shape, dtype, device) and overwritten by later ones.  With several devices the tensor's device picks the engine.
+        The call only enqueues, on the stream step() uses; a policy inside capture_loop may make it.  At the next sync(): an error
+        (RW_ERR_INVALID_ARG, as for unpack_obs_device) for an index outside 0 .. n-1 (that image is zeros), IndexError where a gathered record's state made the reference raise for a
+        requested AGENT_DIRECTION / AGENT_LOAD layer (that agent wrote nothing).
+        AssertionError for a pad_to_shape smaller than the image, ValueError for an unknown layer or dtype, a host tensor, a wrong last
+        dimension, a non-contiguous input, an `out` of the wrong shape, dtype or device."""
+        layers = tuple(ImageLayer(enum_value(l)).value for l in image_layers)
+        if not 1 <= len(layers) <= 8:
+            raise ValueError("global_image_from_records takes 1 to 8 image layers")
+        if not (hasattr(records, "is_cuda") and hasattr(records, "data_ptr")):
+            raise ValueError("global_image_from_records takes torch tensors")
+        import torch as t
+
+        names = {"float32": t.float32, "uint8": t.uint8, "float16": t.float16, "bfloat16": t.bfloat16}
+        tdt = names.get(dtype, dtype) if isinstance(dtype, str) else dtype
+        if tdt not in names.values():
+            raise ValueError(f'dtype must be "float32", "uint8", "float16" or "bfloat16" (or the torch dtype), got {dtype!r}')
+        elem = _capi.GLOBAL_ELEMS[str(tdt).split(".")[-1]]
+        shape = (len(layers),) + tuple(self.grid_size)
+        if pad_to_shape is not None:
+            pad_to_shape = tuple(int(v) for v in pad_to_shape)
+            assert len(pad_to_shape) == 3 and all(p >= s for p, s in zip(pad_to_shape, shape))
+            shape = pad_to_shape
+        rb = self.global_record_bytes
+        if records.dtype != t.uint8:
+            raise ValueError(f"records are uint8, got {records.dtype}")
+        if records.dim() < 1 or records.shape[-1] != rb:
+            raise ValueError(f"expected records (..., {rb}), got {tuple(records.shape)}")
+        if not records.is_contiguous():
+            raise ValueError("`records` must be contiguous (do not slice the last dimension or transpose a tape)")
+        n_records = int(np.prod(records.shape[:-1], dtype=np.int64))
+        n = n_records
+        if index is not None:
+            if not hasattr(index, "is_cuda") or index.dtype not in (t.int32, t.int64) or index.dim() != 1 or not index.is_contiguous():
+                raise ValueError("`index` must be a contiguous 1-D int32 or int64 tensor over the flattened records")
+            if index.device != records.device:
+                raise ValueError(f"`index` lives on {index.device}, `records` on {records.device}")
+            n = int(index.shape[0])
+        shape = (n,) + shape
+        if out is not None and not (hasattr(out, "is_cuda") and tuple(out.shape) == shape and out.dtype == tdt and out.device == records.device
+                                    and out.is_contiguous()):
+            raise ValueError(f"`out` must be a contiguous {tdt} tensor of shape {shape} on {records.device}")
+        if not records.is_cuda:
+            raise ValueError("`records` is a host tensor: global_image_from_records works on the device")
+        if self.output != "torch":
+            raise ValueError('global_image_from_records needs output="torch": only such an env enqueues on the stream the tensors are ordered on')
+        if records.device.index not in self.devices:
+            raise ValueError(f"no engine of this env runs on {records.device}")
+        if records.data_ptr() % 16:
+            raise ValueError("`records` must start on a 16-byte boundary")
+        eng = self.engines[self.devices.index(records.device.index)]
+        if out is None:
+            key = (records.device.index, shape, tdt)
+            out = self._record_images.get(key)
+            if out is None:
+                out = self._record_images[key] = t.empty(shape, dtype=tdt, device=records.device)
+        if n:  # (an empty index: nothing to write)
+            eng.global_image_gather(records.data_ptr(), n_records, None if index is None else index.data_ptr(), n, layers, out.data_ptr(),
+                                    pad_to_shape, elem, index is not None and index.dtype == t.int64)
+        self._live_record_images = (records, index, out)  # (alive until the next call: the launch is only enqueued)
+        return out
+
     def close(self, **kwargs):
         if self._multi is not None:
             self._multi.close()
@@ -1183,6 +1299,8 @@ class WarehouseVecEnv(_VectorEnvBase):
         self._tviews = {}
         self._global_images = {}
         self._unpacked, self._live_unpack = {}, None
+        self._global_records, self._record_images = None, {}
+        self._live_global_records = self._live_record_images = None
         self._fast = None          # (the fast path of step() holds the raw engine handle and views of the freed slab)
         self._fast_ok = False
         self._live_actions = None
