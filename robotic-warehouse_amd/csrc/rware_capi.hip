@@ -3,6 +3,9 @@
 // Owns the HBM-resident batched state of `num_envs` warehouses on one HIP device and
 // enqueues the fused step kernel (rware_kernels.h) on one stream.  No CPU fallback exists:
 // without a usable HIP device rw_create fails with RW_ERR_NO_DEVICE.
+// This file is the engine core: construction, the step path, reset and seeding, the buffer access functions, rw_sync, rw_multi.  The
+// learner-side operations — snapshots, packed minibatches, the critic's global state — live in rware_snapshot.h, rware_minibatch.h and
+// rware_global_state.h, kernels and entry points alike; they are included below, behind the internals they use.
 #include <hip/hip_runtime.h>
 #include <unistd.h>
 #include <hip/hip_ext.h>
@@ -121,62 +124,6 @@ struct rw_engine {
     hipDeviceProp_t prop{};
 };
 
-// rw_unpack_obs: packed rows uint32 [n_rows][PW] -> float32 [n_rows][L], bit for bit what RW_BUF_OBS would hold.  One thread per float4
-// of the output.  A float4 that lies inside the bit part of one row (all but ~2 in 18 at sensor_range 1) takes its four bits from one
-// or two packed words, spreads them into four bytes with one multiply (bit j -> byte j) and converts each byte (v_cvt_f32_ubyteN), as
-// the step kernel's expansion does; one that holds a coordinate slot or straddles two rows goes element by element.  The output is a
-// pure stream: non-temporal stores.  `aligned`: the output starts on a 16-byte boundary (else scalar stores).
-namespace rw {
-__device__ __forceinline__ float unpack_elem(const uint32_t *__restrict__ packed, size_t row, int k, int PW, int W, int H, int normalised) {
-    const uint32_t *r = packed + row * (size_t)PW;
-    if (k < 2) {
-        const int v = (int)(k == 0 ? (r[0] & 0xFFFFu) : (r[0] >> 16));
-        if (normalised) return (float)((double)v / (double)((k == 0 ? W : H) - 1));  // coordf of the step kernel (rware/warehouse.py:636-638)
-        return (float)v;
-    }
-    return ((r[1 + (k >> 5)] >> (k & 31)) & 1u) ? 1.0f : 0.0f;
-}
-template <typename Dummy = void>
-__global__ void __launch_bounds__(256) rware_unpack_obs_kernel(const uint32_t *__restrict__ packed, float *__restrict__ out, size_t n_floats,
-                                                                int L, int PW, int W, int H, int normalised, int aligned) {
-    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t f = q << 2;
-    if (f >= n_floats) return;
-    const size_t row = f / (size_t)L;
-    const int k = (int)(f - row * (size_t)L);
-    if (aligned && k >= 2 && k + 3 < L && f + 3 < n_floats) {
-        const uint32_t *r = packed + row * (size_t)PW + 1 + (k >> 5);
-        const int sh = k & 31;
-        const uint32_t lo = r[0], hi = sh > 28 ? r[1] : 0u;  // (sh > 28 implies k + 3 crosses into the next word, which the row still owns: k + 3 < L)
-        const uint32_t nib = funnel_shr(lo, hi, (uint32_t)sh) & 0xFu;
-        const uint32_t b = opaque((nib * 0x00204081u) & 0x01010101u);
-        float4 v;
-        v.x = (float)(b & 0xFFu);
-        v.y = (float)((b >> 8) & 0xFFu);
-        v.z = (float)((b >> 16) & 0xFFu);
-        v.w = (float)(b >> 24);
-        store_f4_nt(reinterpret_cast<float4 *>(out + f), v);
-        return;
-    }
-    float e[4];
-    size_t rw_ = row;
-    int kk = k;
-    const int n = (int)(n_floats - f < 4 ? n_floats - f : 4);
-    for (int j = 0; j < n; ++j) {
-        e[j] = unpack_elem(packed, rw_, kk, PW, W, H, normalised);
-        if (++kk == L) { kk = 0; ++rw_; }
-    }
-    if (aligned && n == 4) {
-        float4 v;
-        v.x = e[0]; v.y = e[1]; v.z = e[2]; v.w = e[3];
-        store_f4_nt(reinterpret_cast<float4 *>(out + f), v);
-    } else {
-        for (int j = 0; j < n; ++j) out[f + j] = e[j];
-    }
-}
-
-}  // namespace rw
-#include "rware_minibatch.h"   // rw_unpack_obs_gather's kernel (uses rw::unpack_elem above)
 namespace rw {
 
 // rw_seed_device / rw_reset_device: SeedSequence(seeds[e]) -> PCG64 state of env e, one lane per env (rw::pcg_seed_state: some sixty
@@ -195,80 +142,7 @@ __global__ void __launch_bounds__(256) rware_seed_kernel(const uint64_t *__restr
     for (int f = 0; f < 6; ++f) rng[(size_t)f * (size_t)B + (size_t)e] = st[f];
 }
 
-// rw_snapshot_restore_indexed: env e <- the rows a snapshot holds for env index[e], piece by piece (state_pieces; the field-major RNG
-// buffer counts as six pieces of 8-byte rows).  A workgroup takes `E` consecutive DESTINATION envs: their indices are read once, into
-// LDS — an index outside -1 .. B-1 becomes -1 there and sets STATUS_RESTORE_INDEX — and then every piece is walked with `lanes`
-// (a power of two, by the row's length) consecutive lanes along one row and the groups of lanes along consecutive envs: for the
-// 8- and 16-byte rows one lane per env, a wavefront on 64 neighbouring rows.  Source row j and destination row e start at unrelated
-// addresses (110-byte shadow rows, 12-byte records), so the access width is chosen per (piece, env): the widest of 16, 8, 4 bytes
-// that the two addresses share modulo and the row holds, bytes otherwise; bytes in front of the destination's first boundary of
-// that width and behind the last.  Every access lies inside row j of the source and row e of the destination: the neighbours belong to
-// envs that may keep their state.  Plain loads and stores; no thread returns before the barrier.
-enum : int { MAX_RESTORE_PIECES = 24 };
-struct RestorePiece {
-    const char *src;      // the snapshot's copy of the piece
-    char *dst;            // the engine's
-    int32_t row_bytes;    // bytes of one env's row ...
-    int32_t stride;       // ... and from one env's row to the next
-    int32_t lanes_log2;   // lanes along one row: 1 << lanes_log2 (at most 64)
-    int32_t rng;          // one of the six RNG columns: left alone under RW_RESTORE_KEEP_RNG
-};
-struct RestoreArgs {
-    RestorePiece pc[MAX_RESTORE_PIECES];
-    int32_t n_pieces, B, E, flags;
-};
-template <typename T>
-__device__ __forceinline__ void copy_as(char *d, const char *s) { *reinterpret_cast<T *>(d) = *reinterpret_cast<const T *>(s); }
-template <typename Dummy = void>
-__global__ void __launch_bounds__(256) rware_restore_indexed_kernel(const int32_t *__restrict__ index, int32_t *status, const RestoreArgs a) {
-    extern __shared__ __align__(16) int32_t smem[];   // [E] the source slot of every env of this workgroup, -1: keeps its state
-    const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
-    const int e0 = (int)blockIdx.x * a.E;
-    const int ne = a.B - e0 < a.E ? a.B - e0 : a.E;  // (the last workgroup may be ragged; the launch has ceil(B / E) of them: ne >= 1)
-    for (int i = tid; i < ne; i += nt) {
-        int j = index[e0 + i];
-        if (j < -1 || j >= a.B) {
-            atomicOr(status, (int)STATUS_RESTORE_INDEX);
-            j = -1;
-        }
-        smem[i] = j;
-    }
-    __syncthreads();
-    for (int p = 0; p < a.n_pieces; ++p) {
-        const RestorePiece pc = a.pc[p];
-        if (pc.rng && (a.flags & 1)) continue;        // RW_RESTORE_KEEP_RNG (uniform)
-        const int n = pc.row_bytes, sub = tid & ((1 << pc.lanes_log2) - 1), lanes = 1 << pc.lanes_log2;
-        for (int slot = tid >> pc.lanes_log2; slot < ne; slot += nt >> pc.lanes_log2) {
-            const int j = smem[slot];
-            if (j < 0) continue;
-            const char *const s = pc.src + (size_t)j * (size_t)pc.stride;
-            char *const d = pc.dst + (size_t)(e0 + slot) * (size_t)pc.stride;
-            const unsigned rel = (unsigned)(reinterpret_cast<uintptr_t>(s) ^ reinterpret_cast<uintptr_t>(d));
-            const int w = !(rel & 15u) && n >= 16 ? 16 : !(rel & 7u) && n >= 8 ? 8 : !(rel & 3u) && n >= 4 ? 4 : 1;
-            int head = (int)((0u - (unsigned)reinterpret_cast<uintptr_t>(d)) & (unsigned)(w - 1));  // bytes in front of d's first w-byte boundary
-            if (head > n) head = n;
-            const int body = (n - head) / w, tail0 = head + body * w;   // `body` w-byte pieces, then n - tail0 bytes
-            const int items = head + body + (n - tail0);
-            for (int i = sub; i < items; i += lanes) {
-                if (i < head) {
-                    d[i] = s[i];
-                } else if (i < head + body) {
-                    const int o = head + (i - head) * w;
-                    if (w == 16) copy_as<int4>(d + o, s + o);
-                    else if (w == 8) copy_as<uint64_t>(d + o, s + o);
-                    else if (w == 4) copy_as<uint32_t>(d + o, s + o);
-                    else d[o] = s[o];
-                } else {
-                    const int o = tail0 + (i - head - body);
-                    d[o] = s[o];
-                }
-            }
-        }
-    }
-}
-
 }  // namespace rw
-#include "rware_global_state.h"   // rw_global_image, rw_global_records, rw_global_image_gather: the kernels and their two shared halves
 
 namespace {
 
@@ -1485,375 +1359,18 @@ int rw_copy_to_host(rw_engine *eng, void *host_dst, const void *dev_src, size_t 
 
 }  // extern "C"
 
-struct rw_snapshot {
-    void *mem = nullptr;
-    size_t bytes = 0;
-};
-
-namespace {
-// the state that reset()/step() evolve: (device pointer, size) pieces in a fixed order
-std::vector<std::pair<void *, size_t>> state_pieces(rw_engine *eng) {
-    // (the STATE rows of kKinds, by kind — empty without their flag; RW_BUF_OBS / RW_BUF_OBS_PACKED are outputs, not state: a restore
-    //  recomputes them, OP_OBS, in the engine's format)
-    std::vector<std::pair<void *, size_t>> v;
-    v.emplace_back(eng->d_rec, (size_t)eng->prm.B * eng->prm.N * sizeof(uint32_t));  // the agents: their packed records
-    v.emplace_back(eng->d_cnt, (size_t)eng->prm.B * 2 * sizeof(int32_t));            // steps, inactive, pending resets: the counter records
-    for (const Kind &k : kKinds)
-        if (k.role == STATE) v.emplace_back(eng->buf[k.kind].ptr, eng->buf[k.kind].bytes);
-    v.emplace_back(eng->d_shadow, (size_t)eng->prm.B * eng->prm.HW * (eng->wide ? 2 : 1));
-    return v;
-}
-}  // namespace
+// What a learner calls between steps, one header per feature — its kernels, then its entry points and their host helpers (they use the
+// engine internals above: rw_engine, fail, RW_HIP, launch, ALL_VIEWS, kKinds).  Not among the sources bench.kernel_sources_sha() hashes.
+#include "rware_snapshot.h"      // rw_snapshot_create / _save / _restore / _restore_indexed / _destroy
+#include "rware_minibatch.h"     // rw_unpack_obs, rw_unpack_obs_gather
+#include "rware_global_state.h"  // rw_global_image, rw_global_record_bytes, rw_global_records, rw_global_image_gather (after rware_minibatch.h)
 
 extern "C" {
-
-int rw_snapshot_create(rw_engine *eng, rw_snapshot **out) {
-    if (!eng || !out) return RW_ERR_INVALID_ARG;
-    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    rw_snapshot *s = new (std::nothrow) rw_snapshot();
-    if (!s) return fail(eng, RW_ERR_HIP, "out of host memory");
-    for (auto &pc : state_pieces(eng)) s->bytes += (pc.second + 255) & ~(size_t)255;
-    if (hipMalloc(&s->mem, s->bytes) != hipSuccess) {
-        delete s;
-        return fail(eng, RW_ERR_HIP, "hipMalloc of a %zu-byte snapshot failed", s->bytes);
-    }
-    *out = s;
-    return RW_OK;
-}
-
-int rw_snapshot_save(rw_engine *eng, rw_snapshot *snap) {
-    if (!eng || !snap || !snap->mem) return RW_ERR_INVALID_ARG;
-    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    size_t off = 0;
-    for (auto &pc : state_pieces(eng)) {
-        if (pc.second) RW_HIP(eng, hipMemcpyAsync((char *)snap->mem + off, pc.first, pc.second, hipMemcpyDeviceToDevice, eng->stream));
-        off += (pc.second + 255) & ~(size_t)255;
-    }
-    return RW_OK;
-}
-
-int rw_snapshot_restore(rw_engine *eng, const rw_snapshot *snap) {
-    if (!eng || !snap || !snap->mem) return RW_ERR_INVALID_ARG;
-    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    size_t off = 0;
-    for (auto &pc : state_pieces(eng)) {
-        if (pc.second) RW_HIP(eng, hipMemcpyAsync(pc.first, (const char *)snap->mem + off, pc.second, hipMemcpyDeviceToDevice, eng->stream));
-        off += (pc.second + 255) & ~(size_t)255;
-    }
-    eng->stale = ALL_VIEWS;  // (the views are not part of a snapshot: they are derived from what is)
-    return launch(eng, eng->la, rw::OP_OBS);
-}
-
-int rw_snapshot_restore_indexed(rw_engine *eng, const rw_snapshot *snap, const int32_t *src_index_dev, int32_t flags) {
-    // One launch of rware_restore_indexed_kernel and the observation launch of rw_snapshot_restore, both on the engine's stream, and
-    // nothing else: the piece table and the flags travel in the kernel's arguments and the host never reads the index array, so the
-    // call is legal inside a stream capture and is replayed with the graph.
-    if (!eng) return RW_ERR_INVALID_ARG;
-    if (!snap || !snap->mem || !src_index_dev)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_snapshot_restore_indexed: NULL %s", !src_index_dev ? "src_index_dev" : "snapshot");
-    if (reinterpret_cast<uintptr_t>(src_index_dev) & 3u)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_snapshot_restore_indexed: src_index_dev has to be 4-byte aligned");
-    if (flags & ~(int32_t)RW_RESTORE_KEEP_RNG)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_snapshot_restore_indexed: unknown flag bits 0x%x", (unsigned)(flags & ~(int32_t)RW_RESTORE_KEEP_RNG));
-    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    const size_t B = (size_t)eng->prm.B;
-    rw::RestoreArgs a{};
-    size_t off = 0, env_bytes = 0;
-    auto add = [&](const char *src, void *dst, size_t row, bool rng) {
-        rw::RestorePiece &pc = a.pc[a.n_pieces++];
-        pc.src = src;
-        pc.dst = (char *)dst;
-        pc.row_bytes = pc.stride = (int32_t)row;
-        while (pc.lanes_log2 < 6 && ((size_t)16 << pc.lanes_log2) < row) ++pc.lanes_log2;  // a lane per 16 bytes of the row, at most a wavefront
-        pc.rng = rng ? 1 : 0;
-        env_bytes += row;
-    };
-    for (auto &pc : state_pieces(eng)) {
-        const char *src = (const char *)snap->mem + off;
-        off += (pc.second + 255) & ~(size_t)255;
-        if (!pc.second) continue;
-        const bool rng = pc.first == eng->buf[RW_BUF_RNG].ptr;   // field-major uint64 [6][B]: six columns of 8-byte rows
-        const int cols = rng ? 6 : 1;
-        const size_t row = pc.second / B / (size_t)cols;
-        if (a.n_pieces + cols > rw::MAX_RESTORE_PIECES || row * B * (size_t)cols != pc.second || row > 0x7fffffffu)
-            return fail(eng, RW_ERR_UNSUPPORTED, "rw_snapshot_restore_indexed: a state piece of %zu bytes does not fit the piece table", pc.second);
-        for (int c = 0; c < cols; ++c) add(src + (size_t)c * B * row, (char *)pc.first + (size_t)c * B * row, row, rng);
-    }
-    a.B = (int32_t)B;
-    a.E = 64;      // a wavefront of neighbouring envs for the one-lane-per-env pieces
-    a.flags = flags;
-    const unsigned n_wg = (unsigned)((B + (size_t)a.E - 1) / (size_t)a.E);
-    // (a workgroup that has little to copy is one wavefront)
-    const unsigned threads = std::min<size_t>(B, (size_t)a.E) * env_bytes >= 16384 ? 256u : 64u;
-    hipLaunchKernelGGL((rw::rware_restore_indexed_kernel<>), dim3(n_wg), dim3(threads), sizeof(int32_t) * (size_t)a.E, eng->stream, src_index_dev,
-                       eng->d_status, a);
-    RW_HIP(eng, hipGetLastError());
-    eng->stale = ALL_VIEWS;
-    return launch(eng, eng->la, rw::OP_OBS);
-}
-
-int rw_snapshot_destroy(rw_engine *eng, rw_snapshot *snap) {
-    if (!eng) return RW_ERR_INVALID_ARG;
-    if (!snap) return RW_OK;
-    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    RW_HIP(eng, hipStreamSynchronize(eng->stream));
-    if (snap->mem) (void)hipFree(snap->mem);
-    delete snap;
-    return RW_OK;
-}
 
 int rw_refresh_obs(rw_engine *eng) {
     if (!eng) return RW_ERR_INVALID_ARG;
     RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
     return launch(eng, eng->la, rw::OP_OBS);
-}
-
-int rw_unpack_obs(rw_engine *eng, const uint32_t *packed_dev, float *obs_f32_dev, int64_t n_rows) {
-    if (!eng || n_rows < 0 || (n_rows && (!packed_dev || !obs_f32_dev))) return RW_ERR_INVALID_ARG;
-    if (eng->image)  // (RW_OBS_IMAGE_U8 included: a uint8 image needs no unpacking)
-        return fail(eng, RW_ERR_UNSUPPORTED, "rw_unpack_obs: packed rows exist for FLATTENED observations only");
-    if (n_rows == 0) return RW_OK;
-    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    const size_t n_floats = (size_t)n_rows * (size_t)eng->L, n_q = (n_floats + 3) / 4;
-    const size_t blocks = (n_q + 255) / 256;
-    if (blocks > 0x7fffffffu) return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs: %lld rows are more than one launch holds; unpack in slices", (long long)n_rows);
-    const int aligned = (reinterpret_cast<uintptr_t>(obs_f32_dev) & 15u) == 0 ? 1 : 0;
-    hipLaunchKernelGGL((rw::rware_unpack_obs_kernel<>), dim3((unsigned)blocks), dim3(256), 0, eng->stream, packed_dev, obs_f32_dev, n_floats,
-                       eng->L, eng->PW, eng->prm.W, eng->prm.H, eng->prm.normalised, aligned);
-    RW_HIP(eng, hipGetLastError());
-    return RW_OK;
-}
-
-int rw_unpack_obs_gather(rw_engine *eng, const uint32_t *packed_dev, int64_t n_groups, int32_t rows_per_group, const void *index_dev,
-                         int64_t n_index, int32_t elem, int32_t flags, void *out_dev) {
-    // One launch of rware_unpack_gather_kernel on the engine's stream and nothing else: the host never reads the index array, so the call
-    // is legal inside a stream capture and is replayed with the graph.
-    if (!eng) return RW_ERR_INVALID_ARG;
-    if (eng->image)  // (RW_OBS_IMAGE_U8 included)
-        return fail(eng, RW_ERR_UNSUPPORTED, "rw_unpack_obs_gather: packed rows exist for FLATTENED observations only");
-    if (!packed_dev || !out_dev) return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: NULL %s", !packed_dev ? "packed_dev" : "out_dev");
-    if (n_groups < 0 || n_index < 0 || rows_per_group < 1)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: n_groups %lld, n_index %lld, rows_per_group %d", (long long)n_groups,
-                    (long long)n_index, (int)rows_per_group);
-    if (elem != RW_UNPACK_F32 && elem != RW_UNPACK_F16 && elem != RW_UNPACK_BF16)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: unknown element type %d", (int)elem);
-    if (flags & ~(int32_t)RW_UNPACK_INDEX64)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: unknown flag bits 0x%x", (unsigned)(flags & ~(int32_t)RW_UNPACK_INDEX64));
-    if (!index_dev && n_index != n_groups)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: without an index n_index (%lld) has to be n_groups (%lld)", (long long)n_index,
-                    (long long)n_groups);
-    const int index64 = (flags & RW_UNPACK_INDEX64) ? 1 : 0;
-    const unsigned elem_bytes = elem == RW_UNPACK_F32 ? 4u : 2u;
-    if ((reinterpret_cast<uintptr_t>(packed_dev) & 3u) || (reinterpret_cast<uintptr_t>(index_dev) & (index64 ? 7u : 3u)) ||
-        (reinterpret_cast<uintptr_t>(out_dev) & (elem_bytes - 1u)))
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: packed_dev has to be 4-byte aligned, index_dev and out_dev to their elements");
-    // one thread per 16 bytes of output, 256 a workgroup, at most 2^31 - 1 workgroups; the source rows are addressed in size_t words
-    const uint64_t per_group = (uint64_t)rows_per_group * (uint64_t)eng->L, chunk = 16u / elem_bytes;
-    const uint64_t max_elems = (uint64_t)0x7fffffffu * 256u * chunk;
-    if ((uint64_t)n_index > max_elems / per_group || (uint64_t)n_groups > ((uint64_t)1 << 52) / ((uint64_t)rows_per_group * (uint64_t)eng->PW))
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_unpack_obs_gather: %lld groups of %d rows are more than one launch holds; unpack in slices",
-                    (long long)std::max(n_index, n_groups), (int)rows_per_group);
-    if (n_index == 0) return RW_OK;
-    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    rw::UnpackGatherArgs a{};
-    a.packed = packed_dev;
-    a.index = index_dev;
-    a.out = out_dev;
-    a.n_elems = (uint64_t)n_index * per_group;
-    a.n_groups = n_groups;
-    a.inv_L = 1.0 / (double)eng->L;
-    a.inv_G = 1.0 / (double)rows_per_group;
-    a.status = eng->d_status;
-    a.G = rows_per_group;
-    a.L = eng->L;
-    a.PW = eng->PW;
-    a.W = eng->prm.W;
-    a.H = eng->prm.H;
-    a.normalised = eng->prm.normalised;
-    a.aligned = (reinterpret_cast<uintptr_t>(out_dev) & 15u) == 0 ? 1 : 0;
-    a.index64 = index64;
-    const unsigned blocks = (unsigned)(((a.n_elems + chunk - 1) / chunk + 255) / 256);
-    auto go = [&](auto el) {
-        hipLaunchKernelGGL((rw::rware_unpack_gather_kernel<decltype(el)::value>), dim3(blocks), dim3(256), 0, eng->stream, a);
-    };
-    if (elem == RW_UNPACK_F32) go(std::integral_constant<int, rw::UNPACK_F32>());
-    else if (elem == RW_UNPACK_F16) go(std::integral_constant<int, rw::UNPACK_F16>());
-    else go(std::integral_constant<int, rw::UNPACK_BF16>());
-    RW_HIP(eng, hipGetLastError());
-    return RW_OK;
-}
-
-// What rw_global_image and rw_global_image_gather share: the layer list, the padded shape and the element's alignment, checked and
-// written into `a` (layers, transposed, n_layers, the padded shape and its offsets, phase); `chw`: elements per image.
-static int global_image_plan(rw_engine *eng, const char *who, const int32_t *layers, int32_t n_layers, const int32_t *pad_to_shape,
-                             size_t esize, const void *out_dev, rw::GlobalImageArgs &a, uint64_t &chw) {
-    const rw::Params &p = eng->prm;
-    for (int l = 0; l < n_layers; ++l) {
-        const int v = layers[l];
-        if (v < RW_LAYER_SHELVES || v > RW_LAYER_ACCESSIBLE)  // (the reference: ValueError, rware/warehouse.py:1018)
-            return fail(eng, RW_ERR_INVALID_ARG, "%s: unknown image layer %d", who, v);
-        a.layers |= (uint32_t)v << (4 * l);
-        a.transposed |= v == RW_LAYER_AGENT_DIRECTION ? 1u : v == RW_LAYER_AGENT_LOAD ? 2u : 0u;
-    }
-    const int shape[3] = {n_layers, p.H, p.W};
-    int padded[3], before[3];
-    for (int k = 0; k < 3; ++k) {
-        padded[k] = pad_to_shape ? pad_to_shape[k] : shape[k];
-        if (padded[k] < shape[k])  // (the reference: AssertionError, :1028)
-            return fail(eng, RW_ERR_INVALID_ARG, "%s: pad_to_shape[%d] = %d is smaller than the image's %d", who, k, padded[k], shape[k]);
-        before[k] = (padded[k] - shape[k]) / 2;
-    }
-    chw = (uint64_t)padded[0] * (uint64_t)padded[1] * (uint64_t)padded[2];  // (three factors below 2^31: no overflow)
-    if (chw > (1ull << 30))
-        return fail(eng, RW_ERR_INVALID_ARG, "%s: %llu elements per env are more than one launch holds; slice it (smaller "
-                    "padding, or fewer layers per call)", who, (unsigned long long)chw);
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(out_dev);
-    if (addr % esize) return fail(eng, RW_ERR_INVALID_ARG, "%s: a %s out_dev has to be %d-byte aligned", who, esize == 4 ? "float32" : "16-bit", (int)esize);
-    a.H = p.H; a.W = p.W; a.HW = p.HW; a.N = p.N; a.Q = p.Q; a.S = p.S; a.SW = p.SW; a.n_goals = p.n_goals;
-    a.n_layers = n_layers; a.Cp = padded[0]; a.Hp = padded[1]; a.Wp = padded[2];
-    a.c0 = before[0]; a.h0 = before[1]; a.w0 = before[2];
-    a.phase = (int32_t)((addr / esize) % (16 / esize));
-    return RW_OK;
-}
-// ... and the distance between two 16-byte pieces of one thread, decomposed over [env][C'][H'][W']
-static void global_image_stride(rw::GlobalImageArgs &a, unsigned threads, size_t esize, uint64_t chw) {
-    const uint64_t plane = (uint64_t)a.Hp * (uint64_t)a.Wp;
-    const uint64_t stride = (uint64_t)threads * (16 / esize), in_env = stride % chw, in_plane = in_env % plane;
-    a.de = (int32_t)(stride / chw); a.dch = (int32_t)(in_env / plane);
-    a.dy = (int32_t)(in_plane / a.Wp); a.dx = (int32_t)(in_plane % a.Wp);
-}
-
-int rw_global_image(rw_engine *eng, const int32_t *layers, int32_t n_layers, const int32_t *pad_to_shape, int32_t elem, void *out_dev) {
-    // One launch of rware_global_image_kernel on the engine's stream and nothing else: everything the kernel needs beyond the state
-    // travels in its arguments, so the call is legal inside a stream capture and is replayed with the graph.
-    if (!eng) return RW_ERR_INVALID_ARG;
-    if (!layers || !out_dev) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image: NULL %s", !layers ? "layers" : "out_dev");
-    if (n_layers < 1 || n_layers > rw::MAX_IMAGE_LAYERS) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image: n_layers %d not in 1..8", n_layers);
-    if (elem != 0 && elem != 1) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image: elem %d is neither 0 (float32) nor 1 (uint8)", elem);
-    const rw::Params &p = eng->prm;
-    rw::GlobalImageArgs a{};
-    const size_t esize = elem == 0 ? sizeof(float) : 1;
-    uint64_t chw = 0;
-    if (const int rc = global_image_plan(eng, "rw_global_image", layers, n_layers, pad_to_shape, esize, out_dev, a, chw)) return rc;
-    a.B = p.B;
-    // Envs per workgroup: some 8192 elements to store, within 60 KB of LDS (9 words of table, then per env: the request bitmap, a
-    // word and a byte per cell — at most 51 KB at the 10000 cells rw_create admits) and within what an int indexes.
-    const int words_per_env = p.SW + p.HW + (p.HW + 3) / 4;
-    const int by_work = (int)std::max<uint64_t>(1, 8192 / chw), by_lds = (60 * 1024 / 4 - 8) / words_per_env;
-    a.E = std::max(1, std::min(std::min(p.B, 64), std::min(by_work, by_lds)));
-    const size_t lds = sizeof(int32_t) * (8 + (size_t)a.E * words_per_env);
-    const unsigned n_wg = (unsigned)((p.B + a.E - 1) / a.E);
-    // (a workgroup that has little to store is one wavefront: a 3-env batch does not need four)
-    const unsigned threads = (uint64_t)a.E * std::max<uint64_t>(chw / (16 / esize), (uint64_t)p.HW) >= 1024 ? 256u : 64u;
-    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    global_image_stride(a, threads, esize, chw);
-    const int32_t *goal_cells = reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(eng->d_prm) + offsetof(rw::Params, goal_cells));
-    auto go = [&](auto cell, auto el) {  // (`cell`: the shelf shadow's element type; `el`: the output's)
-        using Cell = decltype(cell);
-        using Elem = decltype(el);
-        hipLaunchKernelGGL((rw::rware_global_image_kernel<Cell, Elem>), dim3(n_wg), dim3(threads), lds, eng->stream, (const Cell *)eng->d_shadow,
-                           (const uint32_t *)eng->d_rec, (const int32_t *)p.queue, goal_cells, eng->d_status, (Elem *)out_dev, a);
-    };
-    if (eng->wide) elem == 0 ? go(uint16_t(), float()) : go(uint16_t(), uint8_t());
-    else elem == 0 ? go(uint8_t(), float()) : go(uint8_t(), uint8_t());
-    RW_HIP(eng, hipGetLastError());
-    return RW_OK;
-}
-
-int32_t rw_global_record_bytes(const rw_engine *eng) {
-    if (!eng) return RW_ERR_INVALID_ARG;
-    return (eng->prm.HW + 1 + 15) & ~15;
-}
-
-int rw_global_records(rw_engine *eng, void *records_dev) {
-    // One launch of rware_global_records_kernel on the engine's stream and nothing else (as rw_global_image); the status word is
-    // neither read nor written.
-    if (!eng) return RW_ERR_INVALID_ARG;
-    if (!records_dev) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_records: NULL records_dev");
-    if (reinterpret_cast<uintptr_t>(records_dev) & 15u)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_records: records_dev has to be 16-byte aligned");
-    const rw::Params &p = eng->prm;
-    const int RB = rw_global_record_bytes(eng);
-    rw::GlobalImageArgs a{};
-    a.B = p.B; a.H = p.H; a.W = p.W; a.HW = p.HW; a.N = p.N; a.Q = p.Q; a.S = p.S; a.SW = p.SW; a.n_goals = p.n_goals;
-    // Envs per workgroup: some 4096 cells to read and as many bytes to store, within 60 KB of LDS (per env: the record, the request
-    // bitmap and a word per cell).
-    const int words_per_env = RB / 4 + p.SW + p.HW;
-    const int by_work = std::max(1, 4096 / p.HW), by_lds = (60 * 1024 / 4) / words_per_env;
-    a.E = std::max(1, std::min(std::min(p.B, 64), std::min(by_work, by_lds)));
-    const size_t lds = sizeof(int32_t) * (size_t)a.E * words_per_env;
-    const unsigned n_wg = (unsigned)((p.B + a.E - 1) / a.E);
-    const unsigned threads = (uint64_t)a.E * (uint64_t)p.HW >= 1024 ? 256u : 64u;
-    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    const int32_t *goal_cells = reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(eng->d_prm) + offsetof(rw::Params, goal_cells));
-    if (eng->wide)
-        hipLaunchKernelGGL((rw::rware_global_records_kernel<uint16_t>), dim3(n_wg), dim3(threads), lds, eng->stream, (const uint16_t *)eng->d_shadow,
-                           (const uint32_t *)eng->d_rec, (const int32_t *)p.queue, goal_cells, (uint8_t *)records_dev, RB, a);
-    else
-        hipLaunchKernelGGL((rw::rware_global_records_kernel<uint8_t>), dim3(n_wg), dim3(threads), lds, eng->stream, (const uint8_t *)eng->d_shadow,
-                           (const uint32_t *)eng->d_rec, (const int32_t *)p.queue, goal_cells, (uint8_t *)records_dev, RB, a);
-    RW_HIP(eng, hipGetLastError());
-    return RW_OK;
-}
-
-int rw_global_image_gather(rw_engine *eng, const uint8_t *records_dev, int64_t n_records, const void *index_dev, int64_t n_index,
-                           const int32_t *layers, int32_t n_layers, const int32_t *pad_to_shape, int32_t elem, int32_t flags, void *out_dev) {
-    // One launch of rware_global_image_gather_kernel on the engine's stream and nothing else: the host never reads the index or a record.
-    if (!eng) return RW_ERR_INVALID_ARG;
-    if (!records_dev || !layers || !out_dev)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: NULL %s", !records_dev ? "records_dev" : !layers ? "layers" : "out_dev");
-    if (n_records < 0 || n_index < 0)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: n_records %lld, n_index %lld", (long long)n_records, (long long)n_index);
-    if (!index_dev && n_index != n_records)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: without an index n_index (%lld) has to be n_records (%lld)",
-                    (long long)n_index, (long long)n_records);
-    if (elem < RW_GLOBAL_F32 || elem > RW_GLOBAL_BF16) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: unknown element type %d", (int)elem);
-    if (flags & ~(int32_t)RW_GLOBAL_INDEX64)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: unknown flag bits 0x%x", (unsigned)(flags & ~(int32_t)RW_GLOBAL_INDEX64));
-    if (n_layers < 1 || n_layers > rw::MAX_IMAGE_LAYERS)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: n_layers %d not in 1..8", n_layers);
-    const int index64 = (flags & RW_GLOBAL_INDEX64) ? 1 : 0;
-    if ((reinterpret_cast<uintptr_t>(records_dev) & 15u) || (reinterpret_cast<uintptr_t>(index_dev) & (index64 ? 7u : 3u)))
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: records_dev has to be 16-byte aligned, index_dev to its element");
-    const size_t esize = elem == RW_GLOBAL_F32 ? 4 : elem == RW_GLOBAL_U8 ? 1 : 2;
-    rw::GlobalImageArgs a{};
-    uint64_t chw = 0;
-    if (const int rc = global_image_plan(eng, "rw_global_image_gather", layers, n_layers, pad_to_shape, esize, out_dev, a, chw)) return rc;
-    const int RB = rw_global_record_bytes(eng);
-    // (image numbers are ints in the kernel; record offsets are size_t bytes)
-    if (n_index > 0x7fffffff || (uint64_t)n_records > ((uint64_t)1 << 52) / (uint64_t)RB)
-        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: %lld images of %lld records are more than one launch holds; gather in slices",
-                    (long long)n_index, (long long)n_records);
-    if (n_index == 0) return RW_OK;
-    a.B = (int32_t)n_index;
-    // Images per workgroup: some 8192 elements to store (as rw_global_image), within 60 KB of LDS (the table, then per image its
-    // record and 8 bytes of index — at most 10 KB at the 10000 cells rw_create admits).
-    const int by_work = (int)std::max<uint64_t>(1, 8192 / chw), by_lds = (60 * 1024 - 32) / (RB + 8);
-    a.E = std::max(1, std::min((int)std::min<int64_t>(n_index, 64), std::min(by_work, by_lds)));
-    const size_t lds = 32 + (size_t)a.E * ((size_t)RB + 8);
-    const unsigned n_wg = (unsigned)((n_index + a.E - 1) / a.E);
-    // (four wavefronts once there are 16 lookups a thread — counted in ELEMENTS, whatever their size: a uint8 store has 16 lookups in
-    //  front of it, and one wavefront per workgroup left the narrow types a quarter of the float32 kernel's waves, 2048 against 8192)
-    const unsigned threads = (uint64_t)a.E * chw >= 4096 ? 256u : 64u;
-    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
-    global_image_stride(a, threads, esize, chw);
-    rw::GlobalGatherArgs g{};
-    g.records = records_dev;
-    g.index = index_dev;
-    g.n_records = n_records;
-    g.RB = RB;
-    g.index64 = index64;
-    auto go = [&](auto el) {
-        using Elem = decltype(el);
-        hipLaunchKernelGGL((rw::rware_global_image_gather_kernel<Elem>), dim3(n_wg), dim3(threads), lds, eng->stream, g, eng->d_status,
-                           (Elem *)out_dev, a);
-    };
-    if (elem == RW_GLOBAL_F32) go(float());
-    else if (elem == RW_GLOBAL_U8) go(uint8_t());
-    else if (elem == RW_GLOBAL_F16) go(rw::F16Bits());
-    else go(rw::BF16Bits());
-    RW_HIP(eng, hipGetLastError());
-    return RW_OK;
 }
 
 int rw_sync(rw_engine *eng) {

@@ -1,7 +1,8 @@
 // The critic's global state on the device: rw_global_image, rw_global_records, rw_global_image_gather (include/rware_hip.h,
 // include/rware_hip_global_state.h).  Included by rware_capi.hip at file scope, after rware_kernels.h (rec_cell / rec_dir / rec_carry,
-// u32x4, store_u4_nt, store_f4_nt, STATUS_*, LAYER_*).  Plain C++ throughout: the host-thread build of tests/emu compiles this file as
-// it is, so the 16-bit element types are written as bit patterns.
+// u32x4, store_u4_nt, store_f4_nt, STATUS_*, LAYER_*), after rware_minibatch.h (gather_index_args) and after the engine
+// internals the host part at the end uses (rw_engine, fail, RW_HIP).  The kernels first, the host part below them.  Plain C++ throughout:
+// the host-thread build of tests/emu compiles this file as it is, so the 16-bit element types are written as bit patterns.
 //
 // Warehouse.get_global_image (rware/warehouse.py:966-1040) is a pure function of ONE code byte per cell,
 //     bit 0 shelf | bit 1 requested | bit 2 agent | bit 3 goal | bit 4 AGENT_LOAD | bits 5..7 AGENT_DIRECTION (dir + 1),
@@ -59,6 +60,17 @@ __device__ __forceinline__ void global_image_put(ElemT *o, uint32_t v) {
     else *o = (ElemT)v;
 }
 
+// s_lut [8], by the first eight threads: layer -> where its value sits in the code byte — SHELVES bit 0, REQUESTS 1, AGENTS 2,
+// AGENT_DIRECTION bits 5..7, AGENT_LOAD 4, GOALS 3, ACCESSIBLE bit 2 inverted —, per channel shift | mask << 8 | xor << 16; a channel
+// beyond the list (padding) reads 0 through a zero mask
+__device__ __forceinline__ void global_image_lut(uint32_t *s_lut, int tid, const GlobalImageArgs &a) {
+    if (tid < 8) {
+        const uint32_t l = (a.layers >> (4 * tid)) & 15u;
+        const uint32_t sh = (0x2345210u >> (4 * l)) & 15u, mask = l == (uint32_t)LAYER_AGENT_DIRECTION ? 7u : 1u;
+        s_lut[tid] = tid < a.n_layers ? sh | mask << 8 | (l == (uint32_t)LAYER_ACCESSIBLE ? 1u : 0u) << 16 : 0u;
+    }
+}
+
 // ---- build: state -> code bytes -------------------------------------------------------------------------------------------------
 // s_zero / n_zero: the workgroup's LDS behind the table, s_req [E][SW] | s_mir [E][HW] | s_codew [E][CQ] in any order (CQ words of code
 // per env, >= ceil(HW / 4)), zeroed here; s_lut [8] or nullptr.  RECORD: both transposed layers whatever `transposed` says, the two
@@ -73,13 +85,7 @@ __device__ __forceinline__ void global_image_build(const CellT *__restrict__ sha
     const uint32_t transposed = RECORD ? 3u : a.transposed;
     uint8_t *const s_code = reinterpret_cast<uint8_t *>(s_codew);
     for (int i = tid; i < n_zero; i += nt) s_zero[i] = 0u;
-    if (s_lut && tid < 8) {
-        // layer -> where its value sits in the code byte: SHELVES bit 0, REQUESTS 1, AGENTS 2, AGENT_DIRECTION bits 5..7, AGENT_LOAD 4,
-        // GOALS 3, ACCESSIBLE bit 2 inverted; a channel beyond the list (padding) reads 0 through a zero mask
-        const uint32_t l = (a.layers >> (4 * tid)) & 15u;
-        const uint32_t sh = (0x2345210u >> (4 * l)) & 15u, mask = l == (uint32_t)LAYER_AGENT_DIRECTION ? 7u : 1u;
-        s_lut[tid] = tid < a.n_layers ? sh | mask << 8 | (l == (uint32_t)LAYER_ACCESSIBLE ? 1u : 0u) << 16 : 0u;
-    }
+    if (s_lut) global_image_lut(s_lut, tid, a);
     __syncthreads();
     for (int idx = tid; idx < ne * a.Q; idx += nt) {
         const int e = idx / a.Q, s = queue[(size_t)e0 * a.Q + idx];
@@ -274,12 +280,8 @@ __global__ void __launch_bounds__(256) rware_global_image_gather_kernel(const Gl
     u32x4 *const s_rec = reinterpret_cast<u32x4 *>(smem + 8);
     const uint8_t *const s_code = reinterpret_cast<const uint8_t *>(s_rec);
     int64_t *const s_src = reinterpret_cast<int64_t *>(smem + 8 + a.E * (RB >> 2));
-    if (tid < 8) {   // (as in global_image_build)
-        const uint32_t l = (a.layers >> (4 * tid)) & 15u;
-        const uint32_t sh = (0x2345210u >> (4 * l)) & 15u, mask = l == (uint32_t)LAYER_AGENT_DIRECTION ? 7u : 1u;
-        s_lut[tid] = tid < a.n_layers ? sh | mask << 8 | (l == (uint32_t)LAYER_ACCESSIBLE ? 1u : 0u) << 16 : 0u;
-    }
-    for (int e = tid; e < ne; e += nt) {
+    global_image_lut(s_lut, tid, a);
+    for (int e = tid; e < ne; e += nt) {   // (as rw::gather_source of rware_minibatch.h, the identity range-checked too)
         const size_t i = (size_t)e0 + (size_t)e;
         int64_t j = !g.index ? (int64_t)i : g.index64 ? static_cast<const int64_t *>(g.index)[i] : (int64_t)static_cast<const int32_t *>(g.index)[i];
         if (j < 0 || j >= g.n_records) {
@@ -304,3 +306,171 @@ __global__ void __launch_bounds__(256) rware_global_image_gather_kernel(const Gl
 }
 
 }  // namespace rw
+
+// ---- host part ----------------------------------------------------------------------------------------------------------------------
+
+// What rw_global_image and rw_global_image_gather share: the layer list, the padded shape and the element's alignment, checked and
+// written into `a` (layers, transposed, n_layers, the padded shape and its offsets, phase); `chw`: elements per image.
+static int global_image_plan(rw_engine *eng, const char *who, const int32_t *layers, int32_t n_layers, const int32_t *pad_to_shape,
+                             size_t esize, const void *out_dev, rw::GlobalImageArgs &a, uint64_t &chw) {
+    const rw::Params &p = eng->prm;
+    for (int l = 0; l < n_layers; ++l) {
+        const int v = layers[l];
+        if (v < RW_LAYER_SHELVES || v > RW_LAYER_ACCESSIBLE)  // (the reference: ValueError, rware/warehouse.py:1018)
+            return fail(eng, RW_ERR_INVALID_ARG, "%s: unknown image layer %d", who, v);
+        a.layers |= (uint32_t)v << (4 * l);
+        a.transposed |= v == RW_LAYER_AGENT_DIRECTION ? 1u : v == RW_LAYER_AGENT_LOAD ? 2u : 0u;
+    }
+    const int shape[3] = {n_layers, p.H, p.W};
+    int padded[3], before[3];
+    for (int k = 0; k < 3; ++k) {
+        padded[k] = pad_to_shape ? pad_to_shape[k] : shape[k];
+        if (padded[k] < shape[k])  // (the reference: AssertionError, :1028)
+            return fail(eng, RW_ERR_INVALID_ARG, "%s: pad_to_shape[%d] = %d is smaller than the image's %d", who, k, padded[k], shape[k]);
+        before[k] = (padded[k] - shape[k]) / 2;
+    }
+    chw = (uint64_t)padded[0] * (uint64_t)padded[1] * (uint64_t)padded[2];  // (three factors below 2^31: no overflow)
+    if (chw > (1ull << 30))
+        return fail(eng, RW_ERR_INVALID_ARG, "%s: %llu elements per env are more than one launch holds; slice it (smaller "
+                    "padding, or fewer layers per call)", who, (unsigned long long)chw);
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(out_dev);
+    if (addr % esize) return fail(eng, RW_ERR_INVALID_ARG, "%s: a %s out_dev has to be %d-byte aligned", who, esize == 4 ? "float32" : "16-bit", (int)esize);
+    a.H = p.H; a.W = p.W; a.HW = p.HW; a.N = p.N; a.Q = p.Q; a.S = p.S; a.SW = p.SW; a.n_goals = p.n_goals;
+    a.n_layers = n_layers; a.Cp = padded[0]; a.Hp = padded[1]; a.Wp = padded[2];
+    a.c0 = before[0]; a.h0 = before[1]; a.w0 = before[2];
+    a.phase = (int32_t)((addr / esize) % (16 / esize));
+    return RW_OK;
+}
+// ... and the distance between two 16-byte pieces of one thread, decomposed over [env][C'][H'][W']
+static void global_image_stride(rw::GlobalImageArgs &a, unsigned threads, size_t esize, uint64_t chw) {
+    const uint64_t plane = (uint64_t)a.Hp * (uint64_t)a.Wp;
+    const uint64_t stride = (uint64_t)threads * (16 / esize), in_env = stride % chw, in_plane = in_env % plane;
+    a.de = (int32_t)(stride / chw); a.dch = (int32_t)(in_env / plane);
+    a.dy = (int32_t)(in_plane / a.Wp); a.dx = (int32_t)(in_plane % a.Wp);
+}
+// the goal cells as the build half reads them: out of the engine's device copy of its parameters
+static const int32_t *goal_cells_dev(const rw_engine *eng) { return reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(eng->d_prm) + offsetof(rw::Params, goal_cells)); }
+
+extern "C" {
+
+int rw_global_image(rw_engine *eng, const int32_t *layers, int32_t n_layers, const int32_t *pad_to_shape, int32_t elem, void *out_dev) {
+    // One launch of rware_global_image_kernel on the engine's stream and nothing else: everything the kernel needs beyond the state
+    // travels in its arguments, so the call is legal inside a stream capture and is replayed with the graph.
+    if (!eng) return RW_ERR_INVALID_ARG;
+    if (!layers || !out_dev) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image: NULL %s", !layers ? "layers" : "out_dev");
+    if (n_layers < 1 || n_layers > rw::MAX_IMAGE_LAYERS) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image: n_layers %d not in 1..8", n_layers);
+    if (elem != 0 && elem != 1) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image: elem %d is neither 0 (float32) nor 1 (uint8)", elem);
+    const rw::Params &p = eng->prm;
+    rw::GlobalImageArgs a{};
+    const size_t esize = elem == 0 ? sizeof(float) : 1;
+    uint64_t chw = 0;
+    if (const int rc = global_image_plan(eng, "rw_global_image", layers, n_layers, pad_to_shape, esize, out_dev, a, chw)) return rc;
+    a.B = p.B;
+    // Envs per workgroup: some 8192 elements to store, within 60 KB of LDS (9 words of table, then per env: the request bitmap, a
+    // word and a byte per cell — at most 51 KB at the 10000 cells rw_create admits) and within what an int indexes.
+    const int words_per_env = p.SW + p.HW + (p.HW + 3) / 4;
+    const int by_work = (int)std::max<uint64_t>(1, 8192 / chw), by_lds = (60 * 1024 / 4 - 8) / words_per_env;
+    a.E = std::max(1, std::min(std::min(p.B, 64), std::min(by_work, by_lds)));
+    const size_t lds = sizeof(int32_t) * (8 + (size_t)a.E * words_per_env);
+    const unsigned n_wg = (unsigned)((p.B + a.E - 1) / a.E);
+    // (a workgroup that has little to store is one wavefront: a 3-env batch does not need four)
+    const unsigned threads = (uint64_t)a.E * std::max<uint64_t>(chw / (16 / esize), (uint64_t)p.HW) >= 1024 ? 256u : 64u;
+    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
+    global_image_stride(a, threads, esize, chw);
+    auto go = [&](auto cell, auto el) {  // (`cell`: the shelf shadow's element type; `el`: the output's)
+        using Cell = decltype(cell);
+        using Elem = decltype(el);
+        hipLaunchKernelGGL((rw::rware_global_image_kernel<Cell, Elem>), dim3(n_wg), dim3(threads), lds, eng->stream, (const Cell *)eng->d_shadow,
+                           (const uint32_t *)eng->d_rec, (const int32_t *)p.queue, goal_cells_dev(eng), eng->d_status, (Elem *)out_dev, a);
+    };
+    if (eng->wide) elem == 0 ? go(uint16_t(), float()) : go(uint16_t(), uint8_t());
+    else elem == 0 ? go(uint8_t(), float()) : go(uint8_t(), uint8_t());
+    RW_HIP(eng, hipGetLastError());
+    return RW_OK;
+}
+
+int32_t rw_global_record_bytes(const rw_engine *eng) {
+    if (!eng) return RW_ERR_INVALID_ARG;
+    return (eng->prm.HW + 1 + 15) & ~15;
+}
+
+int rw_global_records(rw_engine *eng, void *records_dev) {
+    // One launch of rware_global_records_kernel on the engine's stream and nothing else (as rw_global_image); the status word is
+    // neither read nor written.
+    if (!eng) return RW_ERR_INVALID_ARG;
+    if (!records_dev) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_records: NULL records_dev");
+    if (reinterpret_cast<uintptr_t>(records_dev) & 15u)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_records: records_dev has to be 16-byte aligned");
+    const rw::Params &p = eng->prm;
+    const int RB = rw_global_record_bytes(eng);
+    rw::GlobalImageArgs a{};
+    a.B = p.B; a.H = p.H; a.W = p.W; a.HW = p.HW; a.N = p.N; a.Q = p.Q; a.S = p.S; a.SW = p.SW; a.n_goals = p.n_goals;
+    // Envs per workgroup: some 4096 cells to read and as many bytes to store, within 60 KB of LDS (per env: the record, the request
+    // bitmap and a word per cell).
+    const int words_per_env = RB / 4 + p.SW + p.HW;
+    const int by_work = std::max(1, 4096 / p.HW), by_lds = (60 * 1024 / 4) / words_per_env;
+    a.E = std::max(1, std::min(std::min(p.B, 64), std::min(by_work, by_lds)));
+    const size_t lds = sizeof(int32_t) * (size_t)a.E * words_per_env;
+    const unsigned n_wg = (unsigned)((p.B + a.E - 1) / a.E);
+    const unsigned threads = (uint64_t)a.E * (uint64_t)p.HW >= 1024 ? 256u : 64u;
+    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
+    auto go = [&](auto cell) {  // (`cell`: the shelf shadow's element type)
+        hipLaunchKernelGGL((rw::rware_global_records_kernel<decltype(cell)>), dim3(n_wg), dim3(threads), lds, eng->stream, (const decltype(cell) *)eng->d_shadow,
+                           (const uint32_t *)eng->d_rec, (const int32_t *)p.queue, goal_cells_dev(eng), (uint8_t *)records_dev, RB, a);
+    };
+    eng->wide ? go(uint16_t()) : go(uint8_t());
+    RW_HIP(eng, hipGetLastError());
+    return RW_OK;
+}
+
+int rw_global_image_gather(rw_engine *eng, const uint8_t *records_dev, int64_t n_records, const void *index_dev, int64_t n_index,
+                           const int32_t *layers, int32_t n_layers, const int32_t *pad_to_shape, int32_t elem, int32_t flags, void *out_dev) {
+    // One launch of rware_global_image_gather_kernel on the engine's stream and nothing else: the host never reads the index or a record.
+    if (!eng) return RW_ERR_INVALID_ARG;
+    if (!records_dev || !layers || !out_dev)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: NULL %s", !records_dev ? "records_dev" : !layers ? "layers" : "out_dev");
+    if (n_records < 0 || n_index < 0)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: n_records %lld, n_index %lld", (long long)n_records, (long long)n_index);
+    if (elem < RW_GLOBAL_F32 || elem > RW_GLOBAL_BF16) return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: unknown element type %d", (int)elem);
+    if (n_layers < 1 || n_layers > rw::MAX_IMAGE_LAYERS)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: n_layers %d not in 1..8", n_layers);
+    int index64 = 0;
+    const bool aligned = !(reinterpret_cast<uintptr_t>(records_dev) & 15u);
+    if (const int rc = gather_index_args(eng, "rw_global_image_gather", flags, index_dev, n_index, n_records, "n_records", aligned,
+                                         "records_dev has to be 16-byte aligned, index_dev to its element", index64)) return rc;
+    const size_t esize = elem == RW_GLOBAL_F32 ? 4 : elem == RW_GLOBAL_U8 ? 1 : 2;
+    rw::GlobalImageArgs a{};
+    uint64_t chw = 0;
+    if (const int rc = global_image_plan(eng, "rw_global_image_gather", layers, n_layers, pad_to_shape, esize, out_dev, a, chw)) return rc;
+    const int RB = rw_global_record_bytes(eng);
+    // (image numbers are ints in the kernel; record offsets are size_t bytes)
+    if (n_index > 0x7fffffff || (uint64_t)n_records > ((uint64_t)1 << 52) / (uint64_t)RB)
+        return fail(eng, RW_ERR_INVALID_ARG, "rw_global_image_gather: %lld images of %lld records are more than one launch holds; gather in slices",
+                    (long long)n_index, (long long)n_records);
+    if (n_index == 0) return RW_OK;
+    a.B = (int32_t)n_index;
+    // Images per workgroup: some 8192 elements to store (as rw_global_image), within 60 KB of LDS (the table, then per image its
+    // record and 8 bytes of index — at most 10 KB at the 10000 cells rw_create admits).
+    const int by_work = (int)std::max<uint64_t>(1, 8192 / chw), by_lds = (60 * 1024 - 32) / (RB + 8);
+    a.E = std::max(1, std::min((int)std::min<int64_t>(n_index, 64), std::min(by_work, by_lds)));
+    const size_t lds = 32 + (size_t)a.E * ((size_t)RB + 8);
+    const unsigned n_wg = (unsigned)((n_index + a.E - 1) / a.E);
+    // (four wavefronts once there are 16 lookups a thread — counted in ELEMENTS, whatever their size: a uint8 store has 16 lookups in
+    //  front of it, and one wavefront per workgroup left the narrow types a quarter of the float32 kernel's waves, 2048 against 8192)
+    const unsigned threads = (uint64_t)a.E * chw >= 4096 ? 256u : 64u;
+    RW_HIP(eng, hipSetDevice(eng->cfg.device_id));
+    global_image_stride(a, threads, esize, chw);
+    const rw::GlobalGatherArgs g{records_dev, index_dev, n_records, RB, index64};
+    auto go = [&](auto el) {
+        hipLaunchKernelGGL((rw::rware_global_image_gather_kernel<decltype(el)>), dim3(n_wg), dim3(threads), lds, eng->stream, g, eng->d_status,
+                           (decltype(el) *)out_dev, a);
+    };
+    if (elem == RW_GLOBAL_F32) go(float());
+    else if (elem == RW_GLOBAL_U8) go(uint8_t());
+    else if (elem == RW_GLOBAL_F16) go(rw::F16Bits());
+    else go(rw::BF16Bits());
+    RW_HIP(eng, hipGetLastError());
+    return RW_OK;
+}
+
+}  // extern "C"

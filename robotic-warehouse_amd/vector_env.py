@@ -35,7 +35,8 @@ import numpy as np
 from . import _capi
 from .enums import DEFAULT_IMAGE_LAYERS, Action, ImageLayer, ObservationType, RewardType, enum_value
 from .layout import Layout, layout_from_params, layout_from_str, obs_length
-from .packing import packed_words, unpack_obs as _unpack_obs
+from .learner_ops import LearnerOps, _is_tensor_arg, global_image_from_state  # noqa: F401  (global_image_from_state: importable from here as before)
+from .packing import packed_words
 
 try:  # gymnasium is optional (absent in the build image); subclass VectorEnv when present
     import gymnasium as _gym
@@ -69,58 +70,6 @@ def _autoreset_metadata(mode):
 
 STATE_FIELDS = ("grid", "agent_x", "agent_y", "agent_dir", "agent_carry", "agent_delivered",
                 "queue", "steps", "inactive", "rng")
-
-
-def global_image_from_state(state, goals, image_layers, pad_to_shape=None):
-    """`Warehouse.get_global_image` (rware/warehouse.py:966-1040) from a batched get_state() dict: (B, C, H, W) float32.
-    Same quirks: GOALS written as the reference does (its loop variables are swapped twice: the right cells, :1013-1015);
-    AGENT_DIRECTION / AGENT_LOAD indexed `[ag.x, ag.y]` on an (H, W) array (:1003-1011) — the mirrored cell, IndexError when
-    x >= H or y >= W; REQUESTS from the positions of the queued shelves; padding split as in :1023-1039."""
-    grid = np.asarray(state["grid"])
-    B, _, H, W = grid.shape
-    ax, ay = np.asarray(state["agent_x"]), np.asarray(state["agent_y"])
-    rows = np.arange(B)[:, None]
-    layers = []
-    for lt in image_layers:
-        lt = ImageLayer(enum_value(lt))
-        layer = np.zeros((B, H, W), np.float32)
-        if lt == ImageLayer.SHELVES:
-            layer[grid[:, 1] > 0] = 1.0
-        elif lt == ImageLayer.REQUESTS:
-            q = np.asarray(state["queue"])
-            for k in range(q.shape[1]):
-                layer[np.asarray(grid[:, 1] == q[:, k, None, None]) & (q[:, k, None, None] > 0)] = 1.0
-        elif lt == ImageLayer.AGENTS:
-            layer[grid[:, 0] > 0] = 1.0
-        elif lt in (ImageLayer.AGENT_DIRECTION, ImageLayer.AGENT_LOAD):
-            carry = np.asarray(state["agent_carry"])
-            use = np.ones_like(ax, bool) if lt == ImageLayer.AGENT_DIRECTION else carry > 0
-            if ((ax >= H) | (ay >= W))[use].any():
-                raise IndexError("index out of bounds: AGENT_DIRECTION / AGENT_LOAD are written at [ag.x, ag.y] (rware/warehouse.py:1006,1011)")
-            val = (np.asarray(state["agent_dir"]) + 1).astype(np.float32) if lt == ImageLayer.AGENT_DIRECTION else np.ones_like(ax, np.float32)
-            for i in range(ax.shape[1]):  # agent order: a later agent overwrites an earlier one on the same (mirrored) cell
-                m = use[:, i]
-                layer[rows[m, 0], ax[m, i], ay[m, i]] = val[m, i]
-        elif lt == ImageLayer.GOALS:
-            for gx, gy in goals:
-                layer[:, gy, gx] = 1.0
-        elif lt == ImageLayer.ACCESSIBLE:
-            layer[:] = 1.0
-            layer[rows, ay, ax] = 0.0
-        layers.append(layer)
-    img = np.stack(layers, axis=1)
-    if pad_to_shape is not None:
-        pad = [p - g for p, g in zip(pad_to_shape, img.shape[1:])]
-        assert all(d >= 0 for d in pad)
-        img = np.pad(img, ((0, 0),) + tuple((d // 2, d // 2 if d % 2 == 0 else d // 2 + 1) for d in pad), mode="constant", constant_values=0)
-    return img
-
-
-def _is_tensor_arg(x):
-    """A torch tensor, or a non-empty list / tuple of them (one per shard) — told by duck typing: torch is imported only by output="torch" envs."""
-    if isinstance(x, (list, tuple)):
-        return bool(x) and all(hasattr(v, "is_cuda") and hasattr(v, "data_ptr") for v in x)
-    return hasattr(x, "is_cuda") and hasattr(x, "data_ptr")
 
 
 class _Space:
@@ -157,7 +106,7 @@ class _CapturedLoop:
             self._engine.mark_views_stale()  # the engine's "views are current" flags (grid, agent_* arrays)
 
 
-class WarehouseVecEnv(_VectorEnvBase):
+class WarehouseVecEnv(LearnerOps, _VectorEnvBase):
     metadata = {"render_modes": [], "autoreset_mode": "next_step"}
 
     def __init__(self, num_envs: int, shelf_columns: int = 3, column_height: int = 8, shelf_rows: int = 1,
@@ -291,15 +240,8 @@ class WarehouseVecEnv(_VectorEnvBase):
         self.n_shelves = self.engines[0].S
         self._make_spaces()
         self._tviews = {}
-        self._global_images = {}  # global_image_device (output="torch"): (layers, shape, dtype) -> the tensors it allocated, one per device
         self._live_actions = None
-        self._clone_token = None  # clone_envs' snapshot: allocated on first use, freed in close()
-        self._unpacked = {}  # unpack_obs_device: (device, shape, dtype) -> the tensor it allocated
-        self._live_unpack = None
-        self._global_records = None  # global_records_device (output="torch"): the tensors it allocated, one per device
-        self._record_images = {}  # global_image_from_records: (device, shape, dtype) -> the tensor it allocated
-        self._live_global_records = self._live_record_images = None
-        self._live_index = None
+        self._op_cache, self._op_live = {}, {}  # learner_ops.py: what its operations allocated, per key; what their last launches read and wrote
         self._pool = None
         self._multi = None
         # step()'s fast path: (tensor type, dtype, shape, device, bound C function, engine handle, cached result tuple); only for
@@ -683,94 +625,6 @@ class WarehouseVecEnv(_VectorEnvBase):
                     self.engines[0].step_device(a.data_ptr())
         return _CapturedLoop(g, s, keep, int(steps), self.engines[0], bridge)
 
-    def snapshot(self):
-        """Checkpoint the batched state on the device (grid, agents, queue, counters, RNG streams).
-        Returns an opaque token for restore(); free it with free_snapshot()."""
-        return [eng.snapshot() for eng in self.engines]
-
-    def restore(self, token, index=None, keep_rng=False):
-        """Roll every env back to a snapshot(); the engine then continues bit-identically.
-
-        `index` (B,): env e takes the state the snapshot holds for env index[e]; -1 keeps env e as it is; repeats are allowed (all
-        zeros broadcasts slot 0 to every env).  The copy is a kernel on the env's stream (rw_snapshot_restore_indexed) followed by the
-        observation launch: the call only enqueues.  Two forms:
-          - a CUDA int32 tensor (B,) on the env's device (output="torch"): zero-copy, nothing waits — legal behind a policy and inside
-            capture_loop; int64 is converted with .to(torch.int32); a multi-device env takes a list of one SHARD-LOCAL tensor per
-            device.  A value outside -1 .. B-1 leaves that env untouched and raises at the next sync();
-          - a host integer array of GLOBAL env indices (any output mode): checked here (ValueError for a value outside -1 .. B-1 and
-            for a source on another shard than its destination), made shard-local and uploaded into a buffer each engine keeps.
-        `keep_rng`: every env's RNG stream stays as it is, so clones of one state draw different request replacements; without it
-        clones are identical and stay so under identical actions.  rewards / terminated / truncated are outputs of a step and are
-        left as they are.  Returns the observations, as restore(token) does."""
-        if index is None:
-            if keep_rng:
-                raise ValueError("keep_rng applies to an indexed restore: pass index=")
-            for eng, h in zip(self.engines, token):
-                eng.restore(h)
-            return self._observations()
-        ptrs, keep = self._restore_index(index)
-        for eng, h, p in zip(self.engines, token, ptrs):
-            eng.restore_indexed(h, p, keep_rng)
-        self._live_index = keep  # alive until the next indexed restore replaces them (stream-ordered allocator: see step_async)
-        return self._observations()
-
-    def _restore_index(self, index):
-        """restore()'s index, checked -> (one device pointer per shard, what has to stay alive).  Nothing here waits for the device
-        when the index is a tensor."""
-        t, n = self._torch, len(self.engines)
-        tensors = _is_tensor_arg(index)
-        if tensors:
-            if t is None:
-                raise ValueError('a tensor index needs output="torch": only such an env enqueues on the stream the tensor is ordered on')
-            parts = list(index) if isinstance(index, (list, tuple)) else [index]
-            if len(parts) != n:
-                raise ValueError(f"expected {n} per-device index tensors (shard-local indices), got {len(parts)}")
-            out = []
-            for d, (v, (lo, hi)) in enumerate(zip(parts, self._bounds)):
-                if not v.is_cuda or v.device.index != self.devices[d]:
-                    raise ValueError(f"the index tensor of shard {d} must live on cuda:{self.devices[d]}")
-                if tuple(v.shape) != (hi - lo,):
-                    raise ValueError(f"the index tensor of shard {d} must have shape ({hi - lo},), got {tuple(v.shape)}")
-                if v.dtype not in (t.int32, t.int64):
-                    raise ValueError(f"the index tensor must be int32 or int64, got {v.dtype}")
-                out.append(v.to(t.int32).contiguous())
-            return [v.data_ptr() for v in out], out
-        h = np.asarray(index)
-        if h.dtype.kind not in "iu" or h.shape != (self.num_envs,):
-            raise ValueError(f"index must be an integer array of shape ({self.num_envs},), got {h.dtype} {h.shape}")
-        h = h.astype(np.int64)
-        if ((h < -1) | (h >= self.num_envs)).any():
-            raise ValueError(f"index values must lie in -1 .. {self.num_envs - 1}")
-        local = []
-        for lo, hi in self._bounds:
-            part = h[lo:hi]
-            if ((part >= 0) & ((part < lo) | (part >= hi))).any():
-                raise ValueError("an env can only take a state saved on its own device: a source index on another shard (a cross-device "
-                                 "copy is not supported)")
-            local.append(np.where(part >= 0, part - lo, -1).astype(np.int32))
-        return [eng.upload_index(part) for eng, part in zip(self.engines, local)], None
-
-    def _alloc_clone_token(self):
-        if self._clone_token is None:
-            self._clone_token = [eng.create_snapshot() for eng in self.engines]
-
-    def clone_envs(self, index, keep_rng=False):
-        """Env e becomes a copy of env index[e] AS IT IS NOW (-1: stays itself): a snapshot into a token the env keeps (allocated on
-        first use, freed in close()), then restore(token, index, keep_rng).  Both halves only enqueue, so with a device tensor it
-        can be called behind a policy and inside capture_loop.  `index` and `keep_rng`: as for restore().  Returns the observations."""
-        ptrs, keep = self._restore_index(index)   # (checked before anything is enqueued)
-        self._alloc_clone_token()
-        for eng, h in zip(self.engines, self._clone_token):
-            eng.snapshot(into=h)
-        for eng, h, p in zip(self.engines, self._clone_token, ptrs):
-            eng.restore_indexed(h, p, keep_rng)
-        self._live_index = keep
-        return self._observations()
-
-    def free_snapshot(self, token):
-        for eng, h in zip(self.engines, token):
-            eng.free_snapshot(h)
-
     def trim(self):
         """Releases the device tapes rollout() with host arrays keeps between calls (one rollout(T=100) of 16384 small-4ag
         envs with observations holds ~1.9 GB per shard until then; they are re-allocated on the next such call)."""
@@ -965,72 +819,6 @@ class WarehouseVecEnv(_VectorEnvBase):
         dt = np.int32 if name == "obs_packed" else None
         return torch.as_tensor(self.engines[0].device_array(name, dtype=dt), device=f"cuda:{self.devices[0]}")
 
-    def unpack_obs(self, packed):
-        """Packed rows (..., PW) -> float32 (..., L) with this env's parameters: bit for bit what obs_format="float32" returns.  numpy in
-        -> numpy out; a torch tensor -> a torch tensor on the same device (plain shift / and / cast ops: call it on a minibatch)."""
-        return _unpack_obs(packed, self.grid_size, self.sensor_range, self.msg_bits, self.normalised_coordinates)
-
-    def unpack_obs_device(self, packed, index=None, dtype="float32", out=None):
-        """unpack_obs(packed[index]).to(dtype) in ONE kernel on the env's stream (rw_unpack_obs_gather), without the gathered copy and the
-        intermediates of the tensor-op path: the learner's half of obs_format="packed".  output="torch" only.
-        `packed`: a contiguous CUDA int32 (or uint32) tensor (G0, ..., PW) — a rollout tape reshaped to (T*B, N, PW), the live
-        "obs_packed" (B, N, PW), or plain rows (n, PW); `index`: a 1-D CUDA int32 or int64 tensor over the FIRST dimension (repeats
-        allowed; None: the whole array); `dtype`: "float32" | "float16" | "bfloat16" or the torch dtype — float32 is bit for bit what
-        obs_format="float32" returns, the 16-bit types are that value rounded to nearest even (0 and 1 are exact: only the two
-        coordinates round).  Returns a tensor (n, ..., L): `out` if given (contiguous, of that shape and dtype, on `packed`'s device), else
-        one allocated on the first call per (shape, dtype) and overwritten by later ones.  With several devices the tensor's device picks
-        the engine.  The call only enqueues — on the stream step() uses, so it is ordered with the learner like every other call and a
-        policy inside capture_loop may make it (a replay reads the index tensor's contents at replay time).  An index outside
-        0 .. G0-1 gives rows of zeros and raises at the next sync().  ValueError for a host tensor, a wrong last dimension, a
-        non-contiguous input, an `out` of the wrong shape, dtype or device."""
-        if self.observation_type in (ObservationType.IMAGE, ObservationType.IMAGE_DICT):
-            raise ValueError("packed rows exist for FLATTENED observations only")
-        if not (hasattr(packed, "is_cuda") and hasattr(packed, "data_ptr")):
-            raise ValueError("unpack_obs_device takes torch tensors (numpy rows: unpack_obs)")
-        import torch as t
-
-        names = {"float32": t.float32, "float16": t.float16, "bfloat16": t.bfloat16}
-        tdt = names.get(dtype, dtype) if isinstance(dtype, str) else dtype
-        if tdt not in names.values():
-            raise ValueError(f'dtype must be "float32", "float16" or "bfloat16" (or the torch dtype), got {dtype!r}')
-        elem = _capi.UNPACK_ELEMS[str(tdt).split(".")[-1]]
-        L, pw = obs_length(self.sensor_range, self.msg_bits), packed_words(self.sensor_range, self.msg_bits)
-        if packed.dtype not in (t.int32, getattr(t, "uint32", t.int32)):
-            raise ValueError(f"packed rows are int32 (or uint32) words, got {packed.dtype}")
-        if packed.dim() < 2 or packed.shape[-1] != pw:
-            raise ValueError(f"expected packed rows (G0, ..., {pw}), got {tuple(packed.shape)}")
-        if not packed.is_contiguous():
-            raise ValueError("`packed` must be contiguous (reshape a tape, do not slice or transpose it)")
-        g0, rows = int(packed.shape[0]), int(np.prod(packed.shape[1:-1], dtype=np.int64))
-        n = g0
-        if index is not None:
-            if not hasattr(index, "is_cuda") or index.dtype not in (t.int32, t.int64) or index.dim() != 1 or not index.is_contiguous():
-                raise ValueError("`index` must be a contiguous 1-D int32 or int64 tensor over the first dimension of `packed`")
-            if index.device != packed.device:
-                raise ValueError(f"`index` lives on {index.device}, `packed` on {packed.device}")
-            n = int(index.shape[0])
-        shape = (n,) + tuple(packed.shape[1:-1]) + (L,)
-        if out is not None and not (hasattr(out, "is_cuda") and tuple(out.shape) == shape and out.dtype == tdt and out.device == packed.device
-                                    and out.is_contiguous()):
-            raise ValueError(f"`out` must be a contiguous {tdt} tensor of shape {shape} on {packed.device}")
-        if not packed.is_cuda:
-            raise ValueError("`packed` is a host tensor: unpack_obs_device works on the device (host rows: unpack_obs)")
-        if self.output != "torch":
-            raise ValueError('unpack_obs_device needs output="torch": only such an env enqueues on the stream the tensors are ordered on')
-        if packed.device.index not in self.devices:
-            raise ValueError(f"no engine of this env runs on {packed.device}")
-        eng = self.engines[self.devices.index(packed.device.index)]
-        if out is None:
-            key = (packed.device.index, shape, tdt)
-            out = self._unpacked.get(key)
-            if out is None:
-                out = self._unpacked[key] = t.empty(shape, dtype=tdt, device=packed.device)
-        if out.numel():  # (an empty index or an empty middle dimension: nothing to write)
-            eng.unpack_gather(packed.data_ptr(), g0, rows, None if index is None else index.data_ptr(), n, elem,
-                              index is not None and index.dtype == t.int64, out.data_ptr())
-        self._live_unpack = (packed, index, out)  # (alive until the next call: the launch is only enqueued)
-        return out
-
     # ------------------------------------------------------------------------------- state
     def get_state(self) -> dict:
         """Batched SoA state: grid (B,2,H,W), agent_* (B,N), queue (B,Q), steps/inactive (B,), rng (B,6)."""
@@ -1105,202 +893,15 @@ class WarehouseVecEnv(_VectorEnvBase):
         self.set_state(refresh_obs=False, rng=states)
         self._seeded = True
 
-    def get_global_image(self, image_layers=(ImageLayer.SHELVES, ImageLayer.GOALS), recompute=False, pad_to_shape=None):
-        """Warehouse.get_global_image (:966-1040) for every env: float32 (B, C, H, W) (or (B,) + pad_to_shape), layer by layer
-        as the reference builds them — including its cache (`recompute=False` returns the last image, whatever layers it was
-        built with) and the transposed AGENT_DIRECTION / AGENT_LOAD layers (IndexError where the reference raises it).
-        Host-side, from get_state(): a global-state input for centralised critics, not part of the per-step path."""
-        if not recompute and getattr(self, "global_image", None) is not None:
-            return self.global_image
-        st = self.get_state()
-        self.global_image = global_image_from_state(st, self.goals, image_layers, pad_to_shape)
-        return self.global_image
-
-    def global_image_device(self, image_layers=(ImageLayer.SHELVES, ImageLayer.GOALS), pad_to_shape=None, dtype="float32", out=None):
-        """get_global_image built ON THE DEVICE (rw_global_image): the same image, layer for layer — (B, C, H, W), or (B,) + pad_to_shape —
-        as float32 or uint8 (`dtype`; every element is an integer in 0 .. 4), from the state the current observation describes.  One
-        kernel on the env's stream, which reads what the step kernels keep: no get_state(), no copy of the grid, no cache (every call
-        recomputes; get_global_image and its cache are untouched).
-        output="torch": a CUDA tensor, allocated on the first call per (layers, shape, dtype) and overwritten in place by later ones — or
-        `out`, a contiguous CUDA tensor of that shape and dtype (a slice at any element offset will do).  Nothing waits and nothing
-        visits the host, so a policy inside capture_loop may call it (into a preallocated `out`); the reference's IndexError for the
-        AGENT_DIRECTION / AGENT_LOAD layers (an agent at x >= H or y >= W) surfaces at the next sync(), and such an agent writes nothing.
-        A sharded env returns one tensor per device (`out`: one per device).
-        numpy output: the same kernel into a device scratch array of the engine's, then sync() — IndexError where the reference raises
-        it — and a host array gathered over the shards.
-        AssertionError for a pad_to_shape smaller than the image (:1028), ValueError for an unknown layer (:1018)."""
-        layers = tuple(ImageLayer(enum_value(l)).value for l in image_layers)
-        if not 1 <= len(layers) <= 8:
-            raise ValueError("global_image_device takes 1 to 8 image layers")
-        dt = np.dtype(dtype)
-        if dt not in (np.dtype(np.float32), np.dtype(np.uint8)):
-            raise ValueError('dtype must be "float32" or "uint8"')
-        shape = (len(layers),) + tuple(self.grid_size)
-        if pad_to_shape is not None:
-            pad_to_shape = tuple(int(v) for v in pad_to_shape)
-            assert len(pad_to_shape) == 3 and all(p >= s for p, s in zip(pad_to_shape, shape))
-            shape = pad_to_shape
-        if self.output == "torch":
-            t = self._torch
-            tdt = t.float32 if dt == np.float32 else t.uint8
-            outs = self._global_images.get((layers, shape, dt.str)) if out is None else list(out) if isinstance(out, (list, tuple)) else [out]
-            if outs is None:
-                outs = self._global_images[(layers, shape, dt.str)] = [
-                    t.empty((eng.B,) + shape, dtype=tdt, device=f"cuda:{dev}") for eng, dev in zip(self.engines, self.devices)]
-            if len(outs) != len(self.engines):
-                raise ValueError(f"`out` must hold one tensor per device ({len(self.engines)})")
-            for eng, dev, o in zip(self.engines, self.devices, outs):
-                if not (o.is_cuda and o.device.index == dev and o.dtype == tdt and tuple(o.shape) == (eng.B,) + shape and o.is_contiguous()):
-                    raise ValueError(f"`out` must be a contiguous {tdt} CUDA tensor of shape {(eng.B,) + shape} on device {dev}")
-            for eng, o in zip(self.engines, outs):
-                eng.global_image(layers, o.data_ptr(), pad_to_shape, dt)
-            self._live_global_image = outs  # (a caller's `out` stays alive until the next call: the launch is only enqueued)
-            return outs[0] if len(outs) == 1 else tuple(outs)
-        if out is not None:
-            raise ValueError('`out` is a device tensor: it exists with output="torch" only')
-        parts = [np.empty((eng.B,) + shape, dt) for eng in self.engines]
-        for eng, part in zip(self.engines, parts):
-            eng.global_image(layers, eng.scratch("global_image", part.nbytes).value, pad_to_shape, dt)
-        err = None
-        for eng in self.engines:  # IndexError where the reference's get_global_image raises it — after EVERY shard has been waited for, so
-            try:                  # that no shard keeps a raised flag for a later call
-                eng.sync()
-            except (IndexError, ValueError) as e:
-                err = err or e
-        if err is not None:
-            raise err
-        for eng, part in zip(self.engines, parts):
-            eng.read_scratch("global_image", part)
-        return parts[0] if len(parts) == 1 else np.concatenate(parts, axis=0)
-
-    @property
-    def global_record_bytes(self) -> int:
-        """RB = (H*W + 1 + 15) & ~15: the bytes of one env's global-state record (global_records_device)."""
-        return self.engines[0].global_record_bytes
-
-    def global_records_device(self, out=None):
-        """The critic's global state as BYTE RECORDS (rw_global_records): uint8 (B, RB), one record per env — byte y*W + x the code of cell
-        (x, y) (bit 0 shelf, 1 requested, 2 agent, 3 goal, 4 AGENT_LOAD and 5..7 AGENT_DIRECTION on the mirrored cell), byte H*W two flags
-        (an agent / a carrying agent without a mirrored cell), zeros up to RB (include/rware_hip_global_state.h).  Every layer of
-        get_global_image at about one byte per cell: keep a (T, B, RB) tape of these instead of images and expand only the minibatches
-        the critic draws (global_image_from_records).  One kernel on the env's stream, from the state the current observation describes;
-        it never raises — whether the AGENT_DIRECTION / AGENT_LOAD layers are asked for is decided when records are gathered.
-        output="torch": a CUDA tensor allocated on the first call and overwritten by later ones — or `out`, a contiguous uint8 CUDA tensor
-        (B, RB) whose address is 16-byte aligned (a slot of a (T, B, RB) tape is).  Enqueue only: a policy inside capture_loop may call
-        it (into a preallocated `out`).  A sharded env returns one tensor per device (`out`: one per device).
-        numpy output: the same kernel into a device scratch array of the engine's, then sync(), and a host array gathered over the shards."""
-        rb = self.global_record_bytes
-        if self.output == "torch":
-            t = self._torch
-            outs = self._global_records if out is None else list(out) if isinstance(out, (list, tuple)) else [out]
-            if outs is None:
-                outs = self._global_records = [t.empty((eng.B, rb), dtype=t.uint8, device=f"cuda:{dev}") for eng, dev in zip(self.engines, self.devices)]
-            if len(outs) != len(self.engines):
-                raise ValueError(f"`out` must hold one tensor per device ({len(self.engines)})")
-            for eng, dev, o in zip(self.engines, self.devices, outs):
-                if not (hasattr(o, "is_cuda") and o.is_cuda and o.device.index == dev and o.dtype == t.uint8 and tuple(o.shape) == (eng.B, rb)
-                        and o.is_contiguous() and o.data_ptr() % 16 == 0):
-                    raise ValueError(f"`out` must be a contiguous, 16-byte aligned uint8 CUDA tensor of shape {(eng.B, rb)} on device {dev}")
-            for eng, o in zip(self.engines, outs):
-                eng.global_records(o.data_ptr())
-            self._live_global_records = outs  # (a caller's `out` stays alive until the next call: the launch is only enqueued)
-            return outs[0] if len(outs) == 1 else tuple(outs)
-        if out is not None:
-            raise ValueError('`out` is a device tensor: it exists with output="torch" only')
-        parts = [np.empty((eng.B, rb), np.uint8) for eng in self.engines]
-        for eng, part in zip(self.engines, parts):
-            eng.global_records(eng.scratch("global_records", part.nbytes).value)
-        for eng in self.engines:
-            eng.sync()
-        for eng, part in zip(self.engines, parts):
-            eng.read_scratch("global_records", part)
-        return parts[0] if len(parts) == 1 else np.concatenate(parts, axis=0)
-
-    def global_image_from_records(self, records, index=None, image_layers=(ImageLayer.SHELVES, ImageLayer.GOALS), pad_to_shape=None,
-                                  dtype="float32", out=None):
-        """global_image_device for a MINIBATCH of stored records (rw_global_image_gather): image i is the image of record index[i], layer
-        for layer what get_global_image gave for the state that record was taken from.  output="torch" only.
-        `records`: a contiguous CUDA uint8 tensor (..., RB) — a (T, B, RB) tape counts as T*B records; `index`: a 1-D CUDA int32 or int64
-        tensor over the flattened records (repeats allowed; None: all of them, in order); `dtype`: "float32" | "uint8" | "float16" |
-        "bfloat16" or the torch dtype (every value is an integer in 0 .. 4, exact in all four).  Returns a tensor (n, C', H', W'): `out`
-        if given (contiguous, of that shape and dtype, on `records`' device; any element offset will do), else one allocated on the
-        first call per (shape, dtype, device) and overwritten by later ones.  With several devices the tensor's device picks the engine.
-        The call only enqueues, on the stream step() uses; a policy inside capture_loop may make it.  At the next sync(): an error
-        (RW_ERR_INVALID_ARG, as for unpack_obs_device) for an index outside 0 .. n-1 (that image is zeros), IndexError where a gathered record's state made the reference raise for a
-        requested AGENT_DIRECTION / AGENT_LOAD layer (that agent wrote nothing).
-        AssertionError for a pad_to_shape smaller than the image, ValueError for an unknown layer or dtype, a host tensor, a wrong last
-        dimension, a non-contiguous input, an `out` of the wrong shape, dtype or device."""
-        layers = tuple(ImageLayer(enum_value(l)).value for l in image_layers)
-        if not 1 <= len(layers) <= 8:
-            raise ValueError("global_image_from_records takes 1 to 8 image layers")
-        if not (hasattr(records, "is_cuda") and hasattr(records, "data_ptr")):
-            raise ValueError("global_image_from_records takes torch tensors")
-        import torch as t
-
-        names = {"float32": t.float32, "uint8": t.uint8, "float16": t.float16, "bfloat16": t.bfloat16}
-        tdt = names.get(dtype, dtype) if isinstance(dtype, str) else dtype
-        if tdt not in names.values():
-            raise ValueError(f'dtype must be "float32", "uint8", "float16" or "bfloat16" (or the torch dtype), got {dtype!r}')
-        elem = _capi.GLOBAL_ELEMS[str(tdt).split(".")[-1]]
-        shape = (len(layers),) + tuple(self.grid_size)
-        if pad_to_shape is not None:
-            pad_to_shape = tuple(int(v) for v in pad_to_shape)
-            assert len(pad_to_shape) == 3 and all(p >= s for p, s in zip(pad_to_shape, shape))
-            shape = pad_to_shape
-        rb = self.global_record_bytes
-        if records.dtype != t.uint8:
-            raise ValueError(f"records are uint8, got {records.dtype}")
-        if records.dim() < 1 or records.shape[-1] != rb:
-            raise ValueError(f"expected records (..., {rb}), got {tuple(records.shape)}")
-        if not records.is_contiguous():
-            raise ValueError("`records` must be contiguous (do not slice the last dimension or transpose a tape)")
-        n_records = int(np.prod(records.shape[:-1], dtype=np.int64))
-        n = n_records
-        if index is not None:
-            if not hasattr(index, "is_cuda") or index.dtype not in (t.int32, t.int64) or index.dim() != 1 or not index.is_contiguous():
-                raise ValueError("`index` must be a contiguous 1-D int32 or int64 tensor over the flattened records")
-            if index.device != records.device:
-                raise ValueError(f"`index` lives on {index.device}, `records` on {records.device}")
-            n = int(index.shape[0])
-        shape = (n,) + shape
-        if out is not None and not (hasattr(out, "is_cuda") and tuple(out.shape) == shape and out.dtype == tdt and out.device == records.device
-                                    and out.is_contiguous()):
-            raise ValueError(f"`out` must be a contiguous {tdt} tensor of shape {shape} on {records.device}")
-        if not records.is_cuda:
-            raise ValueError("`records` is a host tensor: global_image_from_records works on the device")
-        if self.output != "torch":
-            raise ValueError('global_image_from_records needs output="torch": only such an env enqueues on the stream the tensors are ordered on')
-        if records.device.index not in self.devices:
-            raise ValueError(f"no engine of this env runs on {records.device}")
-        if records.data_ptr() % 16:
-            raise ValueError("`records` must start on a 16-byte boundary")
-        eng = self.engines[self.devices.index(records.device.index)]
-        if out is None:
-            key = (records.device.index, shape, tdt)
-            out = self._record_images.get(key)
-            if out is None:
-                out = self._record_images[key] = t.empty(shape, dtype=tdt, device=records.device)
-        if n:  # (an empty index: nothing to write)
-            eng.global_image_gather(records.data_ptr(), n_records, None if index is None else index.data_ptr(), n, layers, out.data_ptr(),
-                                    pad_to_shape, elem, index is not None and index.dtype == t.int64)
-        self._live_record_images = (records, index, out)  # (alive until the next call: the launch is only enqueued)
-        return out
-
     def close(self, **kwargs):
         if self._multi is not None:
             self._multi.close()
             self._multi = None
-        if self._clone_token is not None and self.engines:
-            self.free_snapshot(self._clone_token)
-        self._clone_token = self._live_index = None
+        self._release_learner_ops()
         for eng in self.engines:
             eng.close()
         self.engines = []
         self._tviews = {}
-        self._global_images = {}
-        self._unpacked, self._live_unpack = {}, None
-        self._global_records, self._record_images = None, {}
-        self._live_global_records = self._live_record_images = None
         self._fast = None          # (the fast path of step() holds the raw engine handle and views of the freed slab)
         self._fast_ok = False
         self._live_actions = None
