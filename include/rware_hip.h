@@ -60,7 +60,10 @@ extern "C" {
  * rw_global_image expands, written as one uint8 record per env, enqueue only) and rw_global_image_gather (records gathered by a DEVICE
  * index array and expanded into float32, uint8, float16 or bfloat16 images in one launch, enqueue only) with their enums rw_global_elem,
  * rw_global_flags and rw_global_record_flags, declared in rware_hip_global_state.h; no struct, stream flag or buffer kind changes,
- * rw_global_image itself is unchanged. */
+ * rw_global_image itself is unchanged.
+ * Still 4, a compatible addition: one entry point (advantages and returns, GAE(lambda), from a rollout's reward, flag and value tapes in
+ * one launch, enqueue only) with its argument struct rw_gae_args and its enum rw_gae_flags, declared in rware_hip_advantages.h; no
+ * other struct, stream flag or buffer kind changes. */
 #define RW_ABI_VERSION 4
 
 typedef struct rw_engine rw_engine;
@@ -504,6 +507,10 @@ int rw_global_image(rw_engine *eng, const int32_t *layers, int32_t n_layers, con
 /* -- the global state as byte records, and minibatches of images gathered from them: rw_global_records, rw_global_image_gather --- */
 /* (declared in a header of its own, which this one pulls in: a caller includes rware_hip.h and has it) */
 #include "rware_hip_global_state.h"
+
+/* -- GAE(lambda) advantages and returns from the rollout's reward, flag and value tapes, in one launch ---------------------------- */
+/* (declared in a header of its own, which this one pulls in: a caller includes rware_hip.h and has it) */
+#include "rware_hip_advantages.h"
 
 /* wait for everything enqueued; returns RW_ERR_INVALID_ACTION if any step since the last
  * rw_sync saw an out-of-range action (that action was executed as NOOP), else RW_OK */

@@ -4,6 +4,7 @@ semitable/robotic-warehouse: reset / step / FLATTENED observation of `rware.ware
 The directory is named `robotic-warehouse_amd` (not an identifier); import it as `rware_amd`
 (the shim module at the repository root) or via importlib.
 """
+from .advantages import gae
 from .enums import DEFAULT_IMAGE_LAYERS, Action, Direction, ImageLayer, ObservationType, RewardType
 from .layout import Layout, layout_from_params, layout_from_str, obs_length
 from .packing import pack_obs, packed_words, unpack_obs
@@ -13,6 +14,6 @@ from .vector_env import STATE_FIELDS, WarehouseVecEnv
 __all__ = [
     "Action", "Direction", "ImageLayer", "DEFAULT_IMAGE_LAYERS", "ObservationType", "RewardType", "Layout", "layout_from_params",
     "layout_from_str", "obs_length", "all_ids", "env_kwargs", "make_vec", "make_pipelines", "capture_pipelines", "Pipeline", "streams_overlap", "register_gymnasium", "shard_seeds",
-    "WarehouseVecEnv", "STATE_FIELDS", "pack_obs", "unpack_obs", "packed_words",
+    "WarehouseVecEnv", "STATE_FIELDS", "pack_obs", "unpack_obs", "packed_words", "gae",
 ]
 __version__ = "0.1.0"

@@ -210,12 +210,29 @@ GLOBAL_ELEMS = {"float32": GLOBAL_F32, "uint8": GLOBAL_U8, "float16": GLOBAL_F16
 ALL_PROTOTYPES = (PROTOTYPES, RESTORE_PROTOTYPES, MINIBATCH_PROTOTYPES, GLOBAL_STATE_PROTOTYPES)
 
 
+# ... and that of include/rware_hip_advantages.h, a fifth table (tests/test_advantages_header.py): the first of LATER_PROTOTYPES, the
+# tables declare() and load() consult after ALL_PROTOTYPES.
+class RwGaeArgs(C.Structure):
+    """rw_gae_args"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "rewards_dev", "values_dev", "last_values_dev", "terminated_dev", "truncated_dev", "final_values_dev", "prev_ended_dev",
+        "advantages_dev", "returns_dev", "valid_dev")] + [(n, C.c_int32) for n in ("n_steps", "n_envs", "n_agents", "n_heads")] + [
+        ("gamma", C.c_float), ("lam", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+ADVANTAGE_PROTOTYPES = {
+    "rw_gae": (C.c_int, (_vp, _P(RwGaeArgs))),
+}
+GAE_NEXT_STEP, GAE_TEAM_REWARD = 1, 2   # enum rw_gae_flags
+LATER_PROTOTYPES = (ADVANTAGE_PROTOTYPES,)
+
+
 def declare(lib, names=None):
     """Applies PROTOTYPES (all of them, or `names`) to a CDLL and returns the names that library does not export — a parent commit's
     library may be older than this description.  No ABI check: that is load()'s."""
     missing = []
     for name in PROTOTYPES if names is None else names:
-        restype, argtypes = next(t[name] for t in ALL_PROTOTYPES if name in t)
+        restype, argtypes = next(t[name] for t in ALL_PROTOTYPES + LATER_PROTOTYPES if name in t)
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -261,7 +278,7 @@ def load(path: str | None = None):
             "g.build()'` (or `make -C robotic-warehouse_amd/csrc`). There is no CPU fallback.")
     _preload_hip_runtime()
     lib = C.CDLL(path)
-    for name in [n for t in ALL_PROTOTYPES for n in declare(lib, t)]:  # (this tree's own library has every entry point: what ctypes itself says of a missing one)
+    for name in [n for t in ALL_PROTOTYPES + LATER_PROTOTYPES for n in declare(lib, t)]:  # (this tree's own library has every entry point: what ctypes itself says of a missing one)
         raise AttributeError(f"{path}: undefined symbol: {name}")
     if lib.rw_abi_version() != RW_ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.rw_abi_version()} != {RW_ABI_VERSION}")
@@ -581,6 +598,21 @@ class Engine:
         self._check(self.lib.rw_global_image_gather(self._h, C.c_void_p(int(records_ptr or 0)), int(n_records), C.c_void_p(int(index_ptr or 0)),
                                                     int(n_index), ls, len(layers), pad, int(elem), GLOBAL_INDEX64 if index64 else 0,
                                                     C.c_void_p(int(out_ptr or 0))))
+
+    def gae(self, rewards_ptr, values_ptr, last_values_ptr, terminated_ptr, advantages_ptr, n_steps, n_envs, n_agents, n_heads, *,
+            truncated_ptr=0, final_values_ptr=0, prev_ended_ptr=0, returns_ptr=0, valid_ptr=0, gamma=0.99, lam=0.95, next_step=True,
+            team_reward=False):
+        """rw_gae: GAE(lambda) advantages (and returns, and the valid mask) of the DEVICE tapes rewards float32 [T][B][N], values float32
+        [T][B][K], last_values [B][K], terminated / truncated uint8 [T][B], in the operation order include/rware_hip_advantages.h fixes.
+        `next_step`: RW_GAE_NEXT_STEP (the tape of a NEXT_STEP autoreset env; `prev_ended_ptr` uint8 [B] chains it to the tape before),
+        else a truncated end bootstraps from `final_values_ptr` float32 [T][B][K] (0: from 0).  `team_reward`: RW_GAE_TEAM_REWARD.
+        T, B, N, K are the tape's, not the engine's.  Enqueue only, one launch (legal inside a stream capture)."""
+        a = RwGaeArgs(int(rewards_ptr or 0) or None, int(values_ptr or 0) or None, int(last_values_ptr or 0) or None,
+                      int(terminated_ptr or 0) or None, int(truncated_ptr or 0) or None, int(final_values_ptr or 0) or None,
+                      int(prev_ended_ptr or 0) or None, int(advantages_ptr or 0) or None, int(returns_ptr or 0) or None,
+                      int(valid_ptr or 0) or None, int(n_steps), int(n_envs), int(n_agents), int(n_heads), float(gamma), float(lam),
+                      (GAE_NEXT_STEP if next_step else 0) | (GAE_TEAM_REWARD if team_reward else 0), 0)
+        self._check(self.lib.rw_gae(self._h, C.byref(a)))
 
     def device_array(self, name, dtype=None) -> DeviceArray:
         """`dtype`: present the buffer as another dtype of the same width ("obs_packed" as int32 for torch, whose uint32 has no shift ops)."""

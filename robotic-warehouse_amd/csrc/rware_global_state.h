@@ -474,3 +474,7 @@ int rw_global_image_gather(rw_engine *eng, const uint8_t *records_dev, int64_t n
 }
 
 }  // extern "C"
+
+// The next learner-side op, rw_gae.  Included from here and not from rware_capi.hip: that file's code is part of what
+// bench.kernel_sources_sha() identifies the step path's measured evidence by (profiles/pmc_traffic.json), and this op changes nothing there.
+#include "rware_advantages.h"

@@ -1,11 +1,12 @@
 """What a learner calls between steps, as a mixin of `WarehouseVecEnv`: snapshots (restore / clone by index), packed minibatches, the
-critic's global state.  Every device operation only ENQUEUES on the env's stream.  Two dicts on the env: `_op_cache` (what an operation
+critic's global state, advantages and returns.  Every device operation only ENQUEUES on the env's stream.  Two dicts on the env: `_op_cache` (what an operation
 allocated, per key) and `_op_live` (the arguments of its last launch, alive until its next call)."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import _capi
+from .advantages import gae_shapes
 from .enums import ImageLayer, ObservationType, enum_value
 from .layout import obs_length
 from .packing import packed_words, unpack_obs as _unpack_obs
@@ -393,3 +394,72 @@ class LearnerOps:
                                     pad_to_shape, elem, index is not None and index.dtype == t.int64)
         self._op_live["global_image_from_records"] = (records, index, out)  # (alive until the next call: the launch is only enqueued)
         return out
+
+    # ------------------------------------------------------------------------------- advantages and returns
+    def gae_device(self, rewards, values, terminated, truncated=None, last_values=None, final_values=None, prev_ended=None, gamma=0.99,
+                   lam=0.95, team_reward=None, next_step=None, out=None):
+        """GAE(lambda) advantages and returns of a rollout's tapes in ONE kernel on the env's stream (rw_gae) instead of a backward loop of
+        T times five to eight small tensor ops: -> (advantages, returns, valid).  output="torch" only; all arguments CUDA tensors on one
+        device, contiguous.  The numbers are those of rware_amd.gae, bit for bit (include/rware_hip_advantages.h fixes every operation).
+        `rewards`: float32 (T, B, N), the rollout's reward tape.  `values`: float32 (T+1, B, K) or (T+1, B) — V of the observation each
+        step acted on, row T V of the observation after the last step, read in place — or (T, B, K) / (T, B) with `last_values` (B, K) /
+        (B,); K == N a per-agent critic, K == 1 one value per env.  `terminated`, `truncated` (None: none), `prev_ended`: bool or uint8
+        (reinterpreted, not cast), (T, B), (T, B) and (B,).
+        `next_step` (None: this env's autoreset mode): the tape was written under NEXT_STEP autoreset — the step after an episode end is
+        a reset step: advantage 0, returns == values and valid False there; a truncated end bootstraps from values[t + 1], which is
+        V(final obs) in that mode; `prev_ended`, terminated | truncated of the last row of the tape BEFORE this one, says whether step
+        0 is a reset step (None: no).  Otherwise (SAME_STEP, or DISABLED with a masked reset in the loop) a truncated end bootstraps
+        from `final_values` — V(final_obs), the shape of values[:T], read only where truncated and not terminated — or from 0.
+        `team_reward` (None: K == 1 and N > 1): every head sees the env's summed reward.
+        Returns float32 advantages and returns of the shape of values[:T] and a bool (T, B) mask: `out`, a triple of such tensors
+        (slices of larger buffers will do as long as they are contiguous), else tensors allocated on the first call per shape and
+        overwritten by later ones.  With several devices the device of `rewards` picks the engine; B is the tape's, not the env's.
+        The call only enqueues, on the stream step() uses; a policy inside capture_loop or any captured region may make it (a replay
+        reads the tensors' contents at replay time).  ValueError for host tensors, wrong shapes or dtypes, non-contiguous inputs, an
+        `out` of the wrong shape, dtype or device, gamma or lam outside [0, 1]."""
+        if not all(hasattr(x, "is_cuda") and hasattr(x, "data_ptr") for x in (rewards, values, terminated)):
+            raise ValueError("gae_device takes torch tensors (numpy tapes: rware_amd.gae)")
+        import torch as t
+
+        is_t = lambda x: hasattr(x, "is_cuda") and hasattr(x, "data_ptr")
+        T, B, N, K, shape = gae_shapes(tuple(rewards.shape), tuple(values.shape), None if last_values is None else tuple(getattr(last_values, "shape", ())))
+        if not (0.0 <= float(gamma) <= 1.0 and 0.0 <= float(lam) <= 1.0):
+            raise ValueError(f"gamma ({gamma}) and lam ({lam}) must lie in [0, 1]")
+        team = (K == 1 and N > 1) if team_reward is None else bool(team_reward)
+        if K == 1 and N > 1 and not team:
+            raise ValueError("one value head over several agents needs team_reward")
+        ns = self.autoreset_mode == "next_step" if next_step is None else bool(next_step)
+        given = {"rewards": (rewards, (T, B, N), (t.float32,)), "values": (values, tuple(values.shape), (t.float32,)),
+                 "terminated": (terminated, (T, B), (t.bool, t.uint8)), "truncated": (truncated, (T, B), (t.bool, t.uint8)),
+                 "last_values": (last_values, shape[1:], (t.float32,)), "final_values": (final_values, shape, (t.float32,)),
+                 "prev_ended": (prev_ended, (B,), (t.bool, t.uint8))}
+        for name, (x, want, dtypes) in given.items():
+            if x is None:
+                continue
+            if not is_t(x) or tuple(x.shape) != tuple(want) or x.dtype not in dtypes:
+                raise ValueError(f"`{name}` must be a {' or '.join(str(d) for d in dtypes)} tensor of shape {tuple(want)}, got "
+                                 f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+            if not x.is_contiguous():
+                raise ValueError(f"`{name}` must be contiguous")
+            if x.device != rewards.device:
+                raise ValueError(f"`{name}` lives on {x.device}, `rewards` on {rewards.device}")
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 3):
+            raise ValueError("`out` must be a triple (advantages, returns, valid)")
+        o_adv, o_ret, o_valid = out if out is not None else (None, None, None)
+        dev = rewards.device
+        eng, adv = self._minibatch_out("gae_device", rewards, "rewards", " (host tapes: rware_amd.gae)", o_adv, shape, t.float32)
+        if out is None:
+            ret = self._cached(("gae_device", "returns", dev.index, shape), lambda: t.empty(shape, dtype=t.float32, device=dev))
+            valid = self._cached(("gae_device", "valid", dev.index, (T, B)), lambda: t.empty((T, B), dtype=t.bool, device=dev))
+        else:
+            ret, valid = o_ret, o_valid
+            _check_out(ret, shape, t.float32, dev, "contiguous float32 tensor (returns)", dev)
+            _check_out(valid, (T, B), t.bool, dev, "contiguous bool tensor (valid)", dev)
+        ptr = lambda x: 0 if x is None else x.data_ptr()
+        last_ptr = values.data_ptr() + T * B * K * 4 if last_values is None else last_values.data_ptr()   # (row T, in place)
+        eng.gae(rewards.data_ptr(), values.data_ptr(), last_ptr, terminated.data_ptr(), adv.data_ptr(), T, B, N, K,
+                truncated_ptr=ptr(truncated), final_values_ptr=ptr(final_values), prev_ended_ptr=ptr(prev_ended), returns_ptr=ret.data_ptr(),
+                valid_ptr=valid.data_ptr(), gamma=gamma, lam=lam, next_step=ns, team_reward=team)
+        # (alive until the next call: the launch is only enqueued)
+        self._op_live["gae_device"] = (rewards, values, terminated, truncated, last_values, final_values, prev_ended, adv, ret, valid)
+        return adv, ret, valid
