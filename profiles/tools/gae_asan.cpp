@@ -2,36 +2,12 @@
 // "device" arrays are heap blocks of exactly their sizes (redzones on both sides), so a load or store of the kernel outside a tape
 // faults.  Every result is also recomputed here in plain loops, one float operation a statement, and compared bit for bit.  The shapes
 // are those of tests/test_gae.py, crossed with both modes, the optional arrays present and NULL, four (gamma, lambda) and both paths
-// (every array on a 16-byte boundary; the float arrays one element behind one).  Build and run from the repository root:
-//   F="-DRW_NO_JIT -DRW_WITH_PIPE=1 -DRW_STATS_BUILD=1 -O1 -g -std=c++17 -pthread -Itests/emu -Irobotic-warehouse_amd/csrc -Wno-unknown-pragmas \
-//      -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer"
-//   g++ $F -c -x c++ robotic-warehouse_amd/csrc/rware_capi.hip -o /tmp/gae_capi.o
-//   g++ $F -DRW_GENERIC_R=1 -c -x c++ robotic-warehouse_amd/csrc/rware_generic.hip -o /tmp/gae_g1.o
-//   g++ $F -c tests/emu/emu_globals.cpp -o /tmp/gae_glob.o
-//   g++ $F profiles/tools/gae_asan.cpp /tmp/gae_capi.o /tmp/gae_g1.o /tmp/gae_glob.o -o /tmp/gae_asan && /tmp/gae_asan
-// (the exact-shape table groups and sensor ranges 2 .. 5 are stubbed below: rw_gae takes the device and the stream from the engine only)
-#include <hip/hip_runtime.h>
+// (every array on a 16-byte boundary; the float arrays one element behind one).
+// Build, run and compare with profiles/gae_asan.txt: make -C profiles/tools check
+// (the exact-shape table groups and sensor ranges 2 .. 5 are stubbed in asan_driver.h: rw_gae takes the device and the stream from the engine only)
+#include "asan_driver.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <random>
-#include <vector>
-
-#include "../../include/rware_hip.h"
-#include "rware_static_table.h"
-
-namespace rw_tab {
-step_kernel_t generic_r2(bool, bool, bool, bool) { return nullptr; }
-step_kernel_t generic_r3(bool, bool, bool, bool) { return nullptr; }
-step_kernel_t generic_r4(bool, bool, bool, bool) { return nullptr; }
-step_kernel_t generic_r5(bool, bool, bool, bool) { return nullptr; }
-#define STUB(g) const StaticEntry *static_group_##g(int *n) { *n = 0; return nullptr; }
-STUB(0) STUB(1) STUB(2) STUB(3) STUB(4) STUB(5) STUB(6) STUB(7) STUB(8) STUB(9) STUB(10) STUB(11) STUB(12) STUB(13) STUB(14) STUB(15) STUB(16)
-STUB(17) STUB(18)
-bool static_has_stats() { return false; }
-}  // namespace rw_tab
-extern "C" int rw_selftest(int32_t, char *, size_t) { return RW_OK; }
 
 static rw_engine *eng = nullptr;
 static long g_calls = 0, g_elems = 0;
@@ -118,18 +94,9 @@ static void one_case(int T, int B, int N, int K, bool team, bool ns, bool has_tr
 }
 
 int main() {
-    std::vector<uint8_t> hw(11 * 10);
-    for (int y = 0; y < 11; ++y)
-        for (int x = 0; x < 10; ++x) hw[y * 10 + x] = x % 3 == 0 || y == 0 || y == 10 || y % 9 == 8;
-    std::vector<int32_t> goals = {4, 10, 5, 10};
-    rw_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.abi_version = RW_ABI_VERSION; cfg.num_envs = 2; cfg.grid_h = 11; cfg.grid_w = 10; cfg.n_agents = 2; cfg.sensor_range = 1;
-    cfg.request_queue_size = 2; cfg.max_steps = 25; cfg.reward_type = RW_REWARD_INDIVIDUAL; cfg.autoreset_mode = RW_AUTORESET_NEXT_STEP;
-    cfg.n_goals = 2; cfg.envs_per_workgroup = 4; cfg.threads_per_workgroup = 64; cfg.observation_type = RW_OBS_FLATTENED;
-    cfg.stream_flags = RW_JIT_OFF; cfg.highways = hw.data(); cfg.goals_xy = goals.data();
+    const TinyWarehouse wh(2, 11, 10, 2, 2, 25);
     setenv("RWARE_HOOKS", "1", 1);
-    if (rw_create(&cfg, &eng) != RW_OK) { printf("FAILED rw_create: %s\n", rw_last_error(nullptr)); return 1; }
+    eng = wh.create();
     const struct { const char *what; int T, B, N, K; bool team; } shapes[] = {
         {"one", 1, 1, 1, 1, false}, {"6 columns", 2, 3, 2, 2, false}, {"12 columns", 9, 4, 3, 3, false}, {"team, 1 head", 9, 5, 3, 1, true},
         {"team, 3 heads", 9, 4, 3, 3, true}, {"65 agents", 5, 2, 65, 65, false}, {"team, 65 agents", 5, 2, 65, 1, true},

@@ -7,60 +7,80 @@ The group `capi` is rware_capi.hip instead — every kernel of that translation 
 core and the learner-side kernels of rware_snapshot.h, rware_minibatch.h, rware_global_state.h), under its demangled name.
 RWARE_ISA_CSRC=<dir>: compile that csrc directory instead of this tree's (a `git worktree` of another commit);
 RWARE_ISA_JSON=<file>: also write {"hipcc": <hipcc --version>, "kernels": {"g<group> <instantiation>": {inst, ophash, vgpr, sgpr, lds,
-scratch}}} — what tests/golden/isa/static_parent.json holds (tests/test_packed_obs.py compares the tree's builds against it)."""
+scratch}}} — what tests/golden/isa/static_parent.json holds.
+The two steps are functions the tests load this file for (tests/test_packed_obs.py, test_image_u8.py and test_capi_symbols.py): listings()
+compiles groups to assembly, fingerprints() reads the per-kernel figures out of one listing; hipcc_version() is the "hipcc" of the JSON."""
 import hashlib
 import json
 import os
 import re
+import shutil
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CSRC = os.environ.get("RWARE_ISA_CSRC") or os.path.join(ROOT, "robotic-warehouse_amd", "csrc")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+FIGURES = {"vgpr": "NumVgprs", "sgpr": "TotalNumSgprs", "lds": "LDSByteSize", "scratch": "ScratchSize"}
+
+
+def hipcc_version():
+    """The version lines of `hipcc --version` (no install paths)."""
+    out = subprocess.run([HIPCC, "--version"], capture_output=True, text=True).stdout
+    return "\n".join(l for l in out.splitlines() if "version" in l)
+
+
+def listings(out_dir, groups, csrc=CSRC):
+    """Compiles the table groups `groups` of rware_static.hip (`capi`: rware_capi.hip), side by side, to gfx950 assembly under `out_dir`
+    -> {group: path of its listing}."""
+    os.makedirs(out_dir, exist_ok=True)
+    procs = {}
+    for g in groups:
+        s = os.path.join(out_dir, "capi.s" if g == "capi" else f"static_g{g}.s")
+        unit = ["rware_capi.hip"] if g == "capi" else [f"-DRW_STATIC_GROUP={g}", "rware_static.hip"]
+        procs[g] = s, subprocess.Popen(
+            [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + csrc, "-mllvm", "-amdgpu-kernarg-preload-count=16",
+             "--cuda-device-only", "-S", "-o", s] + unit[:-1] + [os.path.join(csrc, unit[-1])], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    for g, (s, p) in procs.items():
+        _, err = p.communicate(timeout=900)
+        assert p.returncode == 0, err.decode()[-2000:]
+    return {g: s for g, (s, _) in procs.items()}
+
+
+def fingerprints(listing, every_kernel=False, figures=FIGURES):
+    """{instantiation: {inst, ophash, vgpr, sgpr, lds, scratch}} per rw::rware_step_kernel of an assembly listing (`every_kernel`: per
+    symbol with a kernel descriptor, under its demangled name): the instruction count, a hash of the opcode sequence and `figures` (key ->
+    the name of a metadata comment of the kernel; -1: not given)."""
+    lines = listing.splitlines()
+    if every_kernel:
+        kernels = {l.split()[1] for l in lines if l.strip().startswith(".amdhsa_kernel ")}
+        starts = [i for i, l in enumerate(lines) if l.split(":")[0] in kernels and re.match(r"^\S+:\s*(;.*)?$", l)]
+    else:
+        starts = [i for i, l in enumerate(lines) if re.match(r"^_ZN2rw17rware_step_kernel.*:\s*(;.*)?$", l)]
+    out = {}
+    for a, b in zip(starts, starts[1:] + [len(lines)]):
+        body = lines[a:b]
+        name = subprocess.run(["c++filt", lines[a].split(":")[0]], capture_output=True, text=True).stdout.strip()
+        name = re.sub(r"^void rw::rware_step_kernel", "", name).split("(")[0]
+        ops = [l.split()[0] for l in body if re.match(r"^\s+[a-z_][a-z0-9_]*(\s|$)", l) and not l.strip().startswith((".", ";"))]
+
+        def meta(key):
+            return next((int(m.group(1)) for l in body for m in [re.match(rf"^; {key}: (\d+)", l)] if m), -1)
+        out[name] = dict({"inst": len(ops), "ophash": hashlib.sha1(" ".join(ops).encode()).hexdigest()[:10]}, **{k: meta(v) for k, v in figures.items()})
+    return out
 
 
 def main():
-    out = sys.argv[1]
     groups = [g if g == "capi" else int(g) for g in sys.argv[2:]] or [0]
-    os.makedirs(out, exist_ok=True)
     record = {}
-    procs = []
-    for g in groups:
-        s = os.path.join(out, "capi.s" if g == "capi" else f"static_g{g}.s")
-        unit = ["rware_capi.hip"] if g == "capi" else [f"-DRW_STATIC_GROUP={g}", "rware_static.hip"]
-        procs.append((g, s, subprocess.Popen(
-            ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + CSRC, "-mllvm",
-             "-amdgpu-kernarg-preload-count=16", "--cuda-device-only", "-S", "-o", s] + unit[:-1] + [os.path.join(CSRC, unit[-1])])))
-    for g, s, p in procs:
-        assert p.wait() == 0
-        lines = open(s).read().splitlines()
-        if g == "capi":  # every kernel of the unit: the symbols that have a kernel descriptor
-            kernels = {l.split()[1] for l in lines if l.strip().startswith(".amdhsa_kernel ")}
-            starts = [i for i, l in enumerate(lines) if l.split(":")[0] in kernels and re.match(r"^\S+:\s*(;.*)?$", l)]
-        else:
-            starts = [i for i, l in enumerate(lines) if re.match(r"^_ZN2rw17rware_step_kernel.*:\s*(;.*)?$", l)]
-        for a, b in zip(starts, starts[1:] + [len(lines)]):
-            body = lines[a:b]
-            name = subprocess.run(["c++filt", lines[a].split(":")[0]], capture_output=True, text=True).stdout.strip()
-            name = re.sub(r"^void rw::rware_step_kernel", "", name).split("(")[0]
-            ops = [l.split()[0] for l in body if re.match(r"^\s+[a-z_][a-z0-9_]*(\s|$)", l) and not l.strip().startswith((".", ";"))]
-            n_inst = len(ops)
-            oph = hashlib.sha1(" ".join(ops).encode()).hexdigest()[:10]
-            def meta(key):
-                for l in body:
-                    m = re.match(rf"^; {key}: (\d+)", l)
-                    if m:
-                        return int(m.group(1))
-                return -1
-            record[f"g{g} {name}"] = {"inst": n_inst, "ophash": oph, "vgpr": meta("NumVgprs"), "sgpr": meta("TotalNumSgprs"),
-                                      "lds": meta("LDSByteSize"), "scratch": meta("ScratchSize")}
-            lds = f" lds {meta('LDSByteSize')}" if g == "capi" else ""
-            print(f"g{g} {name}: inst {n_inst} vgpr {meta('NumVgprs')} sgpr {meta('NumSgprs')} total_sgpr {meta('TotalNumSgprs')} scratch {meta('ScratchSize')}{lds} occ {meta('Occupancy')} ophash {oph}")
+    for g, s in listings(sys.argv[1], groups).items():
+        for name, f in fingerprints(open(s).read(), g == "capi", dict(FIGURES, user_sgpr="NumSgprs", occ="Occupancy")).items():
+            record[f"g{g} {name}"] = {k: f[k] for k in ("inst", "ophash", *FIGURES)}
+            lds = f" lds {f['lds']}" if g == "capi" else ""
+            print(f"g{g} {name}: inst {f['inst']} vgpr {f['vgpr']} sgpr {f['user_sgpr']} total_sgpr {f['sgpr']} scratch {f['scratch']}{lds} occ {f['occ']} ophash {f['ophash']}")
     if os.environ.get("RWARE_ISA_JSON"):
-        ver = subprocess.run(["/opt/rocm/bin/hipcc", "--version"], capture_output=True, text=True).stdout
-        ver = "\n".join(l for l in ver.splitlines() if "version" in l)  # (the version lines only: no install paths)
         with open(os.environ["RWARE_ISA_JSON"], "w") as f:
-            json.dump({"hipcc": ver, "groups": groups, "kernels": record}, f, indent=1, sort_keys=True)
+            json.dump({"hipcc": hipcc_version(), "groups": groups, "kernels": record}, f, indent=1, sort_keys=True)
             f.write("\n")
 
 

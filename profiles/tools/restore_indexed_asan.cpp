@@ -2,42 +2,13 @@
 // no Python).  The snapshot, the engine's buffers and the index array are heap blocks (the index array of exactly num_envs ints, redzones
 // on both sides), the LDS behind a launch's dynamic shared memory is poisoned by the emulation's launch (tests/emu/hip/hip_runtime.h), so
 // an out-of-bounds load, store or LDS index of the gather kernel faults; UBSan reports a misaligned wide access.  Every restore is also
-// recomputed here in plain loops from rw_read's state before and after, and compared.  Build and run from the repository root:
-//   F="-DRW_NO_JIT -DRW_WITH_PIPE=1 -DRW_STATS_BUILD=1 -O1 -g -std=c++17 -pthread -Itests/emu -Irobotic-warehouse_amd/csrc -Wno-unknown-pragmas \
-//      -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer"
-//   g++ $F -c -x c++ robotic-warehouse_amd/csrc/rware_capi.hip -o /tmp/ri_capi.o
-//   g++ $F -DRW_GENERIC_R=1 -c -x c++ robotic-warehouse_amd/csrc/rware_generic.hip -o /tmp/ri_g1.o
-//   g++ $F -c tests/emu/emu_globals.cpp -o /tmp/ri_glob.o
-//   g++ $F profiles/tools/restore_indexed_asan.cpp /tmp/ri_capi.o /tmp/ri_g1.o /tmp/ri_glob.o -o /tmp/restore_indexed_asan && /tmp/restore_indexed_asan
-// (the exact-shape table groups and sensor ranges 2 .. 5 are stubbed below: the generic sensor_range-1 kernel steps the envs)
-#include <hip/hip_runtime.h>
+// recomputed here in plain loops from rw_read's state before and after, and compared.
+// Build, run and compare with profiles/restore_indexed_asan.txt: make -C profiles/tools check
+// (the exact-shape table groups and sensor ranges 2 .. 5 are stubbed in asan_driver.h: the generic sensor_range-1 kernel steps the envs)
+#include "asan_driver.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <random>
-#include <vector>
 
-#include "../../include/rware_hip.h"
-#include "rware_static_table.h"
-
-namespace rw_tab {
-step_kernel_t generic_r2(bool, bool, bool, bool) { return nullptr; }
-step_kernel_t generic_r3(bool, bool, bool, bool) { return nullptr; }
-step_kernel_t generic_r4(bool, bool, bool, bool) { return nullptr; }
-step_kernel_t generic_r5(bool, bool, bool, bool) { return nullptr; }
-#define STUB(g) const StaticEntry *static_group_##g(int *n) { *n = 0; return nullptr; }
-STUB(0) STUB(1) STUB(2) STUB(3) STUB(4) STUB(5) STUB(6) STUB(7) STUB(8) STUB(9) STUB(10) STUB(11) STUB(12) STUB(13) STUB(14) STUB(15) STUB(16)
-STUB(17) STUB(18)
-bool static_has_stats() { return false; }
-}  // namespace rw_tab
-extern "C" int rw_selftest(int32_t, char *, size_t) { return RW_OK; }
-
-#define CK(call)                                                                                          \
-    do {                                                                                                  \
-        const int rc_ = (call);                                                                           \
-        if (rc_ != RW_OK) { printf("FAILED %s -> %d: %s\n", #call, rc_, rw_last_error(eng)); exit(1); }   \
-    } while (0)
 
 // the state as rw_read shows it: one row of bytes per env and kind (RW_BUF_RNG, field-major on the device, transposed to env-major here)
 struct Field { int kind; size_t row; };
@@ -71,18 +42,9 @@ static void play(rw_engine *eng, std::mt19937 &rng, std::vector<int32_t> &act, i
 }
 
 static void run(const char *what, int B, int H, int W, int N, int Q, int M) {
-    std::vector<uint8_t> hw((size_t)H * W);
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) hw[y * W + x] = x % 3 == 0 || y == 0 || y == H - 1 || y % 9 == 8;
-    std::vector<int32_t> goals = {W / 2 - 1, H - 1, W / 2, H - 1};
-    rw_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.abi_version = RW_ABI_VERSION; cfg.num_envs = B; cfg.grid_h = H; cfg.grid_w = W; cfg.n_agents = N; cfg.sensor_range = 1;
-    cfg.request_queue_size = Q; cfg.max_steps = 9; cfg.reward_type = RW_REWARD_INDIVIDUAL; cfg.autoreset_mode = RW_AUTORESET_NEXT_STEP;
-    cfg.n_goals = 2; cfg.envs_per_workgroup = B >= 100 ? 32 : 4; cfg.threads_per_workgroup = 64; cfg.observation_type = RW_OBS_FLATTENED;
-    cfg.msg_bits = M; cfg.stream_flags = RW_JIT_OFF; cfg.highways = hw.data(); cfg.goals_xy = goals.data();
-    rw_engine *eng = nullptr;
-    if (rw_create(&cfg, &eng) != RW_OK) { printf("FAILED rw_create: %s\n", rw_last_error(nullptr)); exit(1); }
+    TinyWarehouse wh(B, H, W, N, Q, 9);
+    wh.cfg.envs_per_workgroup = B >= 100 ? 32 : 4; wh.cfg.msg_bits = M;
+    rw_engine *eng = wh.create();
     rw_info info;
     CK(rw_get_info(eng, &info));
     std::vector<Field> fields = {{RW_BUF_GRID, (size_t)2 * H * W * 4}, {RW_BUF_AGENT_X, (size_t)N * 4}, {RW_BUF_AGENT_Y, (size_t)N * 4},

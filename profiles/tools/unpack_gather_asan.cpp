@@ -2,45 +2,16 @@
 // Python), and the check of its two float32 -> 16-bit conversions.  The packed rows, the index array and the output are heap blocks of
 // exactly their sizes (redzones on both sides), so an out-of-bounds load or store of the kernel faults; UBSan reports a misaligned wide
 // access.  Every output is recomputed here in plain loops — the 16-bit values by frexp / nearbyint, not by the code under test — and compared.
-// Build and run from the repository root:
-//   F="-DRW_NO_JIT -DRW_WITH_PIPE=1 -DRW_STATS_BUILD=1 -O1 -g -std=c++17 -pthread -Itests/emu -Irobotic-warehouse_amd/csrc -Wno-unknown-pragmas \
-//      -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer"
-//   g++ $F -c -x c++ robotic-warehouse_amd/csrc/rware_capi.hip -o /tmp/ug_capi.o
-//   g++ $F -DRW_GENERIC_R=1 -c -x c++ robotic-warehouse_amd/csrc/rware_generic.hip -o /tmp/ug_g1.o
-//   g++ $F -DRW_GENERIC_R=2 -c -x c++ robotic-warehouse_amd/csrc/rware_generic.hip -o /tmp/ug_g2.o
-//   g++ $F -c tests/emu/emu_globals.cpp -o /tmp/ug_glob.o
-//   g++ $F profiles/tools/unpack_gather_asan.cpp /tmp/ug_capi.o /tmp/ug_g1.o /tmp/ug_g2.o /tmp/ug_glob.o -o /tmp/unpack_gather_asan && /tmp/unpack_gather_asan
-// (the exact-shape table groups and sensor ranges 3 .. 5 are stubbed below)
-#include <hip/hip_runtime.h>
+// Build, run and compare with profiles/unpack_gather_asan.txt: make -C profiles/tools check
+// (the exact-shape table groups and sensor ranges 3 .. 5 are stubbed in asan_driver.h)
+#define ASAN_DRIVER_LINKS_GENERIC_R2
+#include "asan_driver.h"
 
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <random>
-#include <vector>
 
-#include "../../include/rware_hip.h"
-#include "rware_static_table.h"
 #define RW_MINIBATCH_CONVERSIONS_ONLY
 #include "rware_minibatch.h"
-
-namespace rw_tab {
-step_kernel_t generic_r3(bool, bool, bool, bool) { return nullptr; }
-step_kernel_t generic_r4(bool, bool, bool, bool) { return nullptr; }
-step_kernel_t generic_r5(bool, bool, bool, bool) { return nullptr; }
-#define STUB(g) const StaticEntry *static_group_##g(int *n) { *n = 0; return nullptr; }
-STUB(0) STUB(1) STUB(2) STUB(3) STUB(4) STUB(5) STUB(6) STUB(7) STUB(8) STUB(9) STUB(10) STUB(11) STUB(12) STUB(13) STUB(14) STUB(15) STUB(16)
-STUB(17) STUB(18)
-bool static_has_stats() { return false; }
-}  // namespace rw_tab
-extern "C" int rw_selftest(int32_t, char *, size_t) { return RW_OK; }
-
-#define CK(call)                                                                                          \
-    do {                                                                                                  \
-        const int rc_ = (call);                                                                           \
-        if (rc_ != RW_OK) { printf("FAILED %s -> %d: %s\n", #call, rc_, rw_last_error(eng)); exit(1); }   \
-    } while (0)
 
 // float -> a 16-bit float of `mant` explicit mantissa bits and minimum normal exponent `emin`, round to nearest even, by frexp / nearbyint
 static uint32_t ref_convert(float v, int mant, int emin, int bias, uint32_t inf) {
@@ -96,19 +67,9 @@ static void check_conversions() {
 }
 
 static void run(const char *what, int H, int W, int sensor_range, int M, int normalised) {
-    std::vector<uint8_t> hw((size_t)H * W);
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) hw[y * W + x] = x % 3 == 0 || y == 0 || y == H - 1;
-    std::vector<int32_t> goals = {W / 2 - 1, H - 1, W / 2, H - 1};
-    rw_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.abi_version = RW_ABI_VERSION; cfg.num_envs = 2; cfg.grid_h = H; cfg.grid_w = W; cfg.n_agents = 2; cfg.sensor_range = sensor_range;
-    cfg.request_queue_size = 2; cfg.max_steps = 9; cfg.reward_type = RW_REWARD_INDIVIDUAL; cfg.autoreset_mode = RW_AUTORESET_NEXT_STEP;
-    cfg.n_goals = 2; cfg.envs_per_workgroup = 4; cfg.threads_per_workgroup = 64; cfg.observation_type = RW_OBS_FLATTENED;
-    cfg.msg_bits = M; cfg.stream_flags = RW_JIT_OFF; cfg.highways = hw.data(); cfg.goals_xy = goals.data();
-    cfg.normalised_coordinates = normalised;
-    rw_engine *eng = nullptr;
-    if (rw_create(&cfg, &eng) != RW_OK) { printf("FAILED rw_create: %s\n", rw_last_error(nullptr)); exit(1); }
+    TinyWarehouse wh(2, H, W, 2, 2, 9, [](int y, int H_) { return y == 0 || y == H_ - 1; });   // (no highway rows inside)
+    wh.cfg.sensor_range = sensor_range; wh.cfg.msg_bits = M; wh.cfg.normalised_coordinates = normalised;
+    rw_engine *eng = wh.create();
     rw_info info;
     CK(rw_get_info(eng, &info));
     const int L = info.obs_length, PW = 1 + (L + 31) / 32;

@@ -3,43 +3,14 @@
 // The LDS behind a launch's dynamic shared memory is poisoned by the emulation's launch (tests/emu/hip/hip_runtime.h), the host arrays
 // are heap blocks of exactly their size, so an out-of-bounds LDS index or store of a kernel faults.  After every step the state is read
 // back and checked for what no step may break: every agent inside the grid, no two on one cell, layer 0 of the grid naming exactly the
-// agents, every carried shelf under its carrier, the queue holding distinct shelf ids.  Build and run from the repository root:
-//   F="-DRW_NO_JIT -DRW_WITH_PIPE=1 -DRW_STATS_BUILD=1 -O1 -g -std=c++17 -pthread -Itests/emu -Irobotic-warehouse_amd/csrc -Wno-unknown-pragmas \
-//      -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer"
-//   g++ $F -c -x c++ robotic-warehouse_amd/csrc/rware_capi.hip -o /tmp/wa_capi.o
-//   g++ $F -DRW_GENERIC_R=1 -c -x c++ robotic-warehouse_amd/csrc/rware_generic.hip -o /tmp/wa_g1.o
-//   g++ $F -c tests/emu/emu_globals.cpp -o /tmp/wa_glob.o
-//   g++ $F profiles/tools/wide_agents_asan.cpp /tmp/wa_capi.o /tmp/wa_g1.o /tmp/wa_glob.o -o /tmp/wide_agents_asan && /tmp/wide_agents_asan
-// (the exact-shape table groups and sensor ranges 2 .. 5 are stubbed below: the generic sensor_range-1 kernel steps the envs)
-#include <hip/hip_runtime.h>
+// agents, every carried shelf under its carrier, the queue holding distinct shelf ids.
+// Build, run and compare with profiles/wide_agents_asan.txt: make -C profiles/tools check
+// (the exact-shape table groups and sensor ranges 2 .. 5 are stubbed in asan_driver.h: the generic sensor_range-1 kernel steps the envs)
+#include "asan_driver.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <random>
 #include <set>
-#include <vector>
 
-#include "../../include/rware_hip.h"
-#include "rware_static_table.h"
-
-namespace rw_tab {
-step_kernel_t generic_r2(bool, bool, bool, bool) { return nullptr; }
-step_kernel_t generic_r3(bool, bool, bool, bool) { return nullptr; }
-step_kernel_t generic_r4(bool, bool, bool, bool) { return nullptr; }
-step_kernel_t generic_r5(bool, bool, bool, bool) { return nullptr; }
-#define STUB(g) const StaticEntry *static_group_##g(int *n) { *n = 0; return nullptr; }
-STUB(0) STUB(1) STUB(2) STUB(3) STUB(4) STUB(5) STUB(6) STUB(7) STUB(8) STUB(9) STUB(10) STUB(11) STUB(12) STUB(13) STUB(14) STUB(15) STUB(16)
-STUB(17) STUB(18)
-bool static_has_stats() { return false; }
-}  // namespace rw_tab
-extern "C" int rw_selftest(int32_t, char *, size_t) { return RW_OK; }
-
-#define CK(call)                                                                                          \
-    do {                                                                                                  \
-        const int rc_ = (call);                                                                           \
-        if (rc_ != RW_OK) { printf("FAILED %s -> %d: %s\n", #call, rc_, rw_last_error(eng)); exit(1); }   \
-    } while (0)
 #define REQUIRE(cond, ...) do { if (!(cond)) { printf("FAILED: " __VA_ARGS__); printf("\n"); exit(1); } } while (0)
 
 static long check_state(rw_engine *eng, int B, int H, int W, int N, int Q, int S) {
@@ -69,19 +40,12 @@ static long check_state(rw_engine *eng, int B, int H, int W, int N, int Q, int S
 }
 
 static void run(const char *what, int B, int H, int W, int N, int Q, int T, int threads, uint32_t flags, int obs_type, int autoreset) {
-    std::vector<uint8_t> hw((size_t)H * W);
+    TinyWarehouse wh(B, H, W, N, Q, 20, [](int y, int H_) { return y == 0 || y >= H_ - 2 || y % 9 == 0; });   // (two highway rows at the bottom)
     int S = 0;
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) S += !(hw[y * W + x] = x % 3 == 0 || y == 0 || y >= H - 2 || y % 9 == 0);
-    std::vector<int32_t> goals = {W / 2 - 1, H - 1, W / 2, H - 1};
-    rw_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.abi_version = RW_ABI_VERSION; cfg.num_envs = B; cfg.grid_h = H; cfg.grid_w = W; cfg.n_agents = N; cfg.sensor_range = 1;
-    cfg.request_queue_size = Q; cfg.max_steps = 20; cfg.reward_type = RW_REWARD_TWO_STAGE; cfg.autoreset_mode = autoreset;
-    cfg.n_goals = 2; cfg.envs_per_workgroup = 4; cfg.threads_per_workgroup = threads; cfg.observation_type = obs_type;
-    cfg.stream_flags = RW_JIT_OFF | flags; cfg.highways = hw.data(); cfg.goals_xy = goals.data();
-    rw_engine *eng = nullptr;
-    if (rw_create(&cfg, &eng) != RW_OK) { printf("FAILED rw_create: %s\n", rw_last_error(nullptr)); exit(1); }
+    for (uint8_t highway : wh.hw) S += !highway;
+    wh.cfg.reward_type = RW_REWARD_TWO_STAGE; wh.cfg.autoreset_mode = autoreset; wh.cfg.threads_per_workgroup = threads;
+    wh.cfg.observation_type = obs_type; wh.cfg.stream_flags = RW_JIT_OFF | flags;
+    rw_engine *eng = wh.create();
     rw_info info;
     CK(rw_get_info(eng, &info));
     REQUIRE(info.build_kind == 0 && info.n_shelves == S, "build kind %d, %d shelves", info.build_kind, info.n_shelves);

@@ -5,6 +5,7 @@ if no HIP device is visible `rw_create` fails with RW_ERR_NO_DEVICE.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -132,8 +133,8 @@ def make_config(*, abi_version=RW_ABI_VERSION, num_envs, layout, n_agents, senso
     return cfg
 
 
-# Every entry point of include/rware_hip.h, once: name -> (restype, argtypes).  tests/test_capi_boundary.py compares the argument lists,
-# the two structures above and the flag values with the header.
+# Every entry point of include/rware_hip.h, once: name -> (restype, argtypes), in declaration order.  tests/test_capi_boundary.py compares
+# the argument lists, the two structures above and the flag values with the header.
 _vp, _i32, _sz, _str, _P = C.c_void_p, C.c_int32, C.c_size_t, C.c_char_p, C.POINTER
 PROTOTYPES = {
     "rw_create": (C.c_int, (_P(RwConfig), _P(_vp))),
@@ -184,34 +185,20 @@ PROTOTYPES = {
     "rw_abi_version": (C.c_int, ()),
 }
 EXPORTS = tuple(PROTOTYPES)
-# The entry points of include/rware_hip_restore.h (which rware_hip.h includes), described the same way; tests/test_restore_header.py
-# compares them with that header.
-RESTORE_PROTOTYPES = {
-    "rw_snapshot_restore_indexed": (C.c_int, (_vp, _vp, _vp, _i32)),
-}
+
+# What the parts of the boundary (include/rware_hip_*.h, which rware_hip.h includes) add to the constants above: their enums' values ...
 RESTORE_KEEP_RNG = 1   # enum rw_restore_flags: RW_RESTORE_KEEP_RNG
-# ... and those of include/rware_hip_minibatch.h, a third table (tests/test_minibatch_header.py).
-MINIBATCH_PROTOTYPES = {
-    "rw_unpack_obs_gather": (C.c_int, (_vp, _vp, C.c_int64, _i32, _vp, C.c_int64, _i32, _i32, _vp)),
-}
 UNPACK_F32, UNPACK_F16, UNPACK_BF16 = 0, 1, 2   # enum rw_unpack_elem
 UNPACK_INDEX64 = 1                              # enum rw_unpack_flags: RW_UNPACK_INDEX64
 UNPACK_ELEMS = {"float32": UNPACK_F32, "float16": UNPACK_F16, "bfloat16": UNPACK_BF16}
-# ... and those of include/rware_hip_global_state.h, a fourth table (tests/test_global_state_header.py); load() declares all four.
-GLOBAL_STATE_PROTOTYPES = {
-    "rw_global_record_bytes": (_i32, (_vp,)),
-    "rw_global_records": (C.c_int, (_vp, _vp)),
-    "rw_global_image_gather": (C.c_int, (_vp, _vp, C.c_int64, _vp, C.c_int64, _P(_i32), _i32, _P(_i32), _i32, _i32, _vp)),
-}
 GLOBAL_F32, GLOBAL_U8, GLOBAL_F16, GLOBAL_BF16 = 0, 1, 2, 3   # enum rw_global_elem (0 and 1: rw_global_image's `elem`)
 GLOBAL_INDEX64 = 1                                            # enum rw_global_flags: RW_GLOBAL_INDEX64
 GLOBAL_RECORD_NO_MIRROR, GLOBAL_RECORD_LOADED_NO_MIRROR = 1, 2   # enum rw_global_record_flags: byte H*W of a record
 GLOBAL_ELEMS = {"float32": GLOBAL_F32, "uint8": GLOBAL_U8, "float16": GLOBAL_F16, "bfloat16": GLOBAL_BF16}
-ALL_PROTOTYPES = (PROTOTYPES, RESTORE_PROTOTYPES, MINIBATCH_PROTOTYPES, GLOBAL_STATE_PROTOTYPES)
+GAE_NEXT_STEP, GAE_TEAM_REWARD = 1, 2   # enum rw_gae_flags
 
 
-# ... and that of include/rware_hip_advantages.h, a fifth table (tests/test_advantages_header.py): the first of LATER_PROTOTYPES, the
-# tables declare() and load() consult after ALL_PROTOTYPES.
+# ... and their one structure
 class RwGaeArgs(C.Structure):
     """rw_gae_args"""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -220,19 +207,43 @@ class RwGaeArgs(C.Structure):
         ("gamma", C.c_float), ("lam", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
-ADVANTAGE_PROTOTYPES = {
-    "rw_gae": (C.c_int, (_vp, _P(RwGaeArgs))),
+# Every header of include/, once: file name -> its entry points (name -> (restype, argtypes), in declaration order), its enums as this
+# module mirrors them (C enum name -> {C member: value}, from the constants above: a member is RW_ + the constant's name, or the name
+# itself) and its structures (C struct name -> ctypes class).  tests/test_capi_parts.py compares every row but the first with its header,
+# as tests/test_capi_boundary.py does the first; declare() and load() look entry points up here, in this order.
+Header = collections.namedtuple("Header", "functions enums structs")
+_enum = lambda *names: {n if n.startswith("RW_") else "RW_" + n: globals()[n] for n in names}
+HEADERS = {
+    "rware_hip.h": Header(PROTOTYPES, {
+        "rw_status": _enum("RW_OK", "RW_ERR_INVALID_ARG", "RW_ERR_INVALID_ACTION", "RW_ERR_HIP", "RW_ERR_UNSUPPORTED", "RW_ERR_NO_DEVICE",
+                           "RW_ERR_INDEX", "RW_ERR_SELFTEST"),
+        "rw_stream_flags": _enum("RW_STREAM_USE_GIVEN", "RW_OBS_STORES_CACHED", "RW_OBS_STORES_STREAM", "RW_JIT_OFF", "RW_JIT_FORCE", "RW_PIPE_OFF",
+                                 "RW_PIPE_ON", "RW_STATS_ON", "RW_PRIO_OFF", "RW_PRIO_ON", "RW_OBS_PACKED", "RW_EPISODES_ON", "RW_ACTION_MASK_ON",
+                                 "RW_OBS_IMAGE_U8", "RW_TIME_LIMIT_TRUNCATES")}, {"rw_config": RwConfig, "rw_info": RwInfo}),
+    "rware_hip_restore.h": Header({
+        "rw_snapshot_restore_indexed": (C.c_int, (_vp, _vp, _vp, _i32)),
+    }, {"rw_restore_flags": _enum("RESTORE_KEEP_RNG")}, {}),
+    "rware_hip_minibatch.h": Header({
+        "rw_unpack_obs_gather": (C.c_int, (_vp, _vp, C.c_int64, _i32, _vp, C.c_int64, _i32, _i32, _vp)),
+    }, {"rw_unpack_elem": _enum("UNPACK_F32", "UNPACK_F16", "UNPACK_BF16"), "rw_unpack_flags": _enum("UNPACK_INDEX64")}, {}),
+    "rware_hip_global_state.h": Header({
+        "rw_global_record_bytes": (_i32, (_vp,)),
+        "rw_global_records": (C.c_int, (_vp, _vp)),
+        "rw_global_image_gather": (C.c_int, (_vp, _vp, C.c_int64, _vp, C.c_int64, _P(_i32), _i32, _P(_i32), _i32, _i32, _vp)),
+    }, {"rw_global_elem": _enum("GLOBAL_F32", "GLOBAL_U8", "GLOBAL_F16", "GLOBAL_BF16"), "rw_global_flags": _enum("GLOBAL_INDEX64"),
+        "rw_global_record_flags": _enum("GLOBAL_RECORD_NO_MIRROR", "GLOBAL_RECORD_LOADED_NO_MIRROR")}, {}),
+    "rware_hip_advantages.h": Header({
+        "rw_gae": (C.c_int, (_vp, _P(RwGaeArgs))),
+    }, {"rw_gae_flags": _enum("GAE_NEXT_STEP", "GAE_TEAM_REWARD")}, {"rw_gae_args": RwGaeArgs}),
 }
-GAE_NEXT_STEP, GAE_TEAM_REWARD = 1, 2   # enum rw_gae_flags
-LATER_PROTOTYPES = (ADVANTAGE_PROTOTYPES,)
 
 
 def declare(lib, names=None):
-    """Applies PROTOTYPES (all of them, or `names`) to a CDLL and returns the names that library does not export — a parent commit's
-    library may be older than this description.  No ABI check: that is load()'s."""
+    """Applies the prototypes of HEADERS (the main header's, or those of `names`) to a CDLL and returns the names that library does not
+    export, in table order — a parent commit's library may be older than this description.  No ABI check: that is load()'s."""
     missing = []
     for name in PROTOTYPES if names is None else names:
-        restype, argtypes = next(t[name] for t in ALL_PROTOTYPES + LATER_PROTOTYPES if name in t)
+        restype, argtypes = next(h.functions[name] for h in HEADERS.values() if name in h.functions)
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -278,7 +289,7 @@ def load(path: str | None = None):
             "g.build()'` (or `make -C robotic-warehouse_amd/csrc`). There is no CPU fallback.")
     _preload_hip_runtime()
     lib = C.CDLL(path)
-    for name in [n for t in ALL_PROTOTYPES + LATER_PROTOTYPES for n in declare(lib, t)]:  # (this tree's own library has every entry point: what ctypes itself says of a missing one)
+    for name in [n for h in HEADERS.values() for n in declare(lib, h.functions)]:  # (this tree's own library has every entry point: what ctypes itself says of a missing one)
         raise AttributeError(f"{path}: undefined symbol: {name}")
     if lib.rw_abi_version() != RW_ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.rw_abi_version()} != {RW_ABI_VERSION}")

@@ -156,3 +156,24 @@ def test_gpu_baseline_of_the_tree_against_itself(tmp_path):
         assert list(rows) == ["a", "b", "a2"], config                                 # one line per leg
         assert rows["a"] == rows["b"] == rows["a2"], config                           # parent and own: the same engine, the same launches
     assert out.read_text().count("the spread") == 2
+
+
+def test_the_further_experiments_resolve_without_a_device():
+    spec = importlib.util.spec_from_file_location("ab_harness_more", os.path.join(ROOT, "profiles", "tools", "ab.py"))
+    ab = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ab)
+    assert set(ab.MORE_EXPERIMENTS) == {"restore_indexed"} and not set(ab.MORE_EXPERIMENTS) & set(ab.EXPERIMENTS)
+    for name, exp in ab.MORE_EXPERIMENTS.items():
+        assert exp["reps"] >= 1 and exp["configs"] and exp["compare"], name
+        for conf in list(exp["configs"].values()) + [s for _, s in exp.get("extras", ())]:
+            rware_amd.env_kwargs(conf["env_id"])                                      # registered (KeyError otherwise)
+            assert conf.get("mode", "step") in ab.NEEDS and conf.get("fn", "step") in ab.LEG_FUNCTIONS
+        for leg in exp["legs"].values():
+            assert leg["lib"] in ("parent", "own") and (leg["mode"] is None or leg["mode"] in ab.NEEDS)
+            assert _capi.stream_flags(**leg["options"]) >= 0
+            assert all(v is True for v in leg["options"].values()), "options are given by keyword, never as numbers"
+        for own, parents in exp["compare"]:
+            assert exp["legs"][own]["lib"] == "own" and parents and all(exp["legs"][p]["lib"] == "parent" for p in parents), name
+    exp = ab.MORE_EXPERIMENTS["restore_indexed"]
+    assert exp["configs"] is ab.THREE and exp["legs"] is ab.PARENT_OWN_PARENT       # the per-step legs are `baseline`'s
+    assert [(s["fn"], s["envs"]) for _, s in exp["extras"]] == [("restore", 16384), ("restore", 262144), ("restore", 16384)]

@@ -2,88 +2,48 @@
 compares every part of that description with include/rware_hip.h: argument lists, struct layouts, flag and status values.  A drift
 there is stack garbage at run time, not an error; here it is a failing CPU test."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
+import c_header as ch
 import rware_amd
 from rware_amd import _capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rware_hip.h")).read(), flags=re.S)
-SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "size_t": C.c_size_t, "char": C.c_char}
-
-
-def c_class(decl):
-    """A C declarator without its name ("const int32_t *", "uint64_t", "char [16]") -> "pointer" or the ctypes scalar type."""
-    if "*" in decl or "[" in decl:
-        return "pointer"
-    return SCALARS[" ".join(w for w in decl.split() if w != "const")]
-
-
-def ctypes_class(t):
-    return "pointer" if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer) else t
-
-
-def header_prototypes():
-    out = {}
-    for ret, name, args in re.findall(r"([A-Za-z_0-9 \*]+?)\b(rw_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", HEADER):
-        args = [] if args.strip() == "void" else [re.sub(r"\b[A-Za-z_0-9]+\s*(\[\d*\])?\s*$", r"\1", a.strip()) for a in args.split(",")]
-        out[name] = (c_class(ret), [c_class(a) for a in args])
-    return out
-
-
-def header_struct(name):
-    """[(field, element ctypes type or "pointer", array length or None)] of `typedef struct name { ... } name;`, comma lists expanded."""
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), HEADER, flags=re.S).group(1)
-    decls = [d.strip() for d in body.split(";") if d.strip()]
-    fields = []
-    for d in decls:
-        first, *more = [p.strip() for p in d.split(",")]
-        base = re.match(r"((?:const\s+)?[A-Za-z_0-9]+)\s", first).group(1)
-        for declarator in [first[len(base):]] + more:
-            m = re.fullmatch(r"\s*(\*?)\s*([A-Za-z_0-9]+)\s*(?:\[(\d+)\])?", declarator)
-            fields.append((m.group(2), "pointer" if m.group(1) else c_class(base), int(m.group(3)) if m.group(3) else None))
-    return len(decls), fields
-
-
-def header_enum(name):
-    body = re.search(r"enum %s \{(.*?)\};" % name, HEADER, flags=re.S).group(1)
-    return {n: int(v) for n, v in re.findall(r"\b(RW_[A-Z_0-9]+)\s*=\s*(-?\d+)", body)}
+HEADER = ch.read("rware_hip.h")
 
 
 def test_prototypes_match_the_header():
-    want = header_prototypes()
+    want = {p.name: (p.ret, p.args) for p in ch.prototypes(HEADER)}
     assert len(want) == 46 and set(_capi.PROTOTYPES) == set(want)
     assert _capi.EXPORTS == tuple(_capi.PROTOTYPES)
     for name, (ret, args) in want.items():
         restype, argtypes = _capi.PROTOTYPES[name]
-        assert ctypes_class(restype) == ret, f"{name}: return type"
+        assert ch.ctypes_class(restype) == ret, f"{name}: return type"
         assert len(argtypes) == len(args), f"{name}: {len(argtypes)} arguments described, {len(args)} declared"
         for k, (got, exp) in enumerate(zip(argtypes, args)):
-            assert ctypes_class(got) == exp, f"{name}: argument {k} is {got}, the header declares {exp}"
+            assert ch.ctypes_class(got) == exp, f"{name}: argument {k} is {got}, the header declares {exp}"
 
 
 @pytest.mark.parametrize("struct, cls, n_decls", [("rw_config", _capi.RwConfig, 24), ("rw_info", _capi.RwInfo, 17)])
 def test_structures_match_the_header(struct, cls, n_decls):
-    n, want = header_struct(struct)
+    n, want = ch.struct(HEADER, struct)
     assert n == n_decls
     got = []
     for field, t in cls._fields_:
         if issubclass(t, C.Array):
             got.append((field, t._type_, t._length_))
         else:
-            got.append((field, ctypes_class(t), None))
+            got.append((field, ch.ctypes_class(t), None))
     assert got == want
 
 
 def test_flags_status_and_version_match_the_header():
-    flags = header_enum("rw_stream_flags")
+    flags = ch.enum(HEADER, "rw_stream_flags")
     assert len(flags) == 15
     consts = {n: v for n, v in vars(_capi).items() if n.startswith("RW_") and isinstance(v, int)}
     status = {n: v for n, v in consts.items() if n == "RW_OK" or n.startswith("RW_ERR_")}
-    assert status == header_enum("rw_status")
+    assert status == ch.enum(HEADER, "rw_status")
     assert consts.pop("RW_ABI_VERSION") == int(re.search(r"#define RW_ABI_VERSION (\d+)", HEADER).group(1))
     assert {n: v for n, v in consts.items() if n not in status} == flags      # names and values, both directions
     for option, table in _capi.STREAM_FLAGS.items():

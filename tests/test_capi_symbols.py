@@ -7,17 +7,15 @@ import re
 import numpy as np
 import pytest
 
+import c_header as ch
 import rware_amd
 from rware_amd import _capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rware_hip.h")
 
 
 def declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(rw_[a-z_0-9]+)\s*\(", src)))
+    return sorted(p.name for p in ch.prototypes(ch.read("rware_hip.h")))
 
 
 def test_header_declares_the_expected_surface():
@@ -80,24 +78,16 @@ def test_kernel_isa_has_no_operand_order_sensitive_dpp_folds(tmp_path):
     written as `x_k - x_me - 1` passed the host emulation and failed a golden trace on the GPU;
     profiles/tools/dpp_subrev_probe.hip shows it in isolation).  The exact-shape kernels may only contain DPP forms whose
     operand order cannot matter."""
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "profiles", "tools", "isa_stats.py"))
+    isa_stats = importlib.util.module_from_spec(spec)     # (the one place that knows how a table group becomes a listing)
+    spec.loader.exec_module(isa_stats)
+    if not os.path.exists(isa_stats.HIPCC):
         pytest.skip("no hipcc on this box")
     csrc = os.path.join(ROOT, "robotic-warehouse_amd", "csrc")
     # the exact-shape kernels live in rware_static.hip, one translation unit per table group: all groups, side by side
     n_groups = int(re.search(r"kStaticGroups = (\d+)", open(os.path.join(csrc, "rware_static_table.h")).read()).group(1))
-    procs = []
-    for g in range(n_groups):
-        procs.append(subprocess.Popen(
-            [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + csrc, "-mllvm", "-amdgpu-kernarg-preload-count=16",
-             f"-DRW_STATIC_GROUP={g}", "--cuda-device-only", "-S", "-o", str(tmp_path / f"static_g{g}.s"),
-             os.path.join(csrc, "rware_static.hip")], stdout=subprocess.PIPE, stderr=subprocess.PIPE))
-    for g, pr in enumerate(procs):
-        _, err = pr.communicate(timeout=900)
-        assert pr.returncode == 0, err.decode()[-2000:]
-    listing = "".join((tmp_path / f"static_g{g}.s").read_text() for g in range(n_groups))
+    listing = "".join(open(path).read() for path in isa_stats.listings(str(tmp_path), range(n_groups)).values())
 
     class _Out:  # (the checks below read one listing)
         @staticmethod
@@ -198,10 +188,6 @@ def test_runtime_specialisation_keeps_no_cache_in_shared_directories(tmp_path):
 def test_header_and_c_example_compile_as_plain_c11():
     """include/rware_hip.h is a C header (the boundary a cgo / JNI / ctypes binding reads): it and examples/rware_c_example.c — the
     boundary used from plain C, no Python, no torch — go through `gcc -std=c11 -pedantic` without a diagnostic."""
-    import subprocess
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for args in (["-x", "c", os.path.join(root, "include", "rware_hip.h")], [os.path.join(root, "examples", "rware_c_example.c")]):
-        out = subprocess.run(["gcc", "-std=c11", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-I", os.path.join(root, "include")] + args,
-                             capture_output=True, text=True)
+    for args in (["-x", "c", os.path.join(ROOT, "include", "rware_hip.h")], [os.path.join(ROOT, "examples", "rware_c_example.c")]):
+        out = ch.gcc(*args)
         assert out.returncode == 0, out.stderr

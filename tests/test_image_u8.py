@@ -7,10 +7,10 @@ The reference in every comparison is the float32 image of the golden fixtures (r
 oracle; every comparison is exact, by value (a uint8 element against the float32 element it stands for), and everything the engine
 hands out is checked to BE uint8."""
 import ctypes as C
+import importlib.util
 import json
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,12 +19,14 @@ import golden_util as gu
 import lockstep as ls
 from engine_backend import EngineBackend, build_emu
 from rware_oracle import OracleVecEnv
-from test_packed_obs import _isa_of
 
 import rware_amd
 from rware_amd import _capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "profiles", "tools", "isa_stats.py"))
+isa_stats = importlib.util.module_from_spec(_spec)      # the tool that recorded tests/golden/isa/*.json: its compile and its figures
+_spec.loader.exec_module(isa_stats)
 pytestmark = pytest.mark.timeout(1500)
 P_ACT = [.1, .5, .15, .15, .1]
 
@@ -335,21 +337,14 @@ def test_ahead_of_time_image_kernels_keep_the_parent_commits_isa(tmp_path):
     group 1 — must come out instruction for instruction as before.  tests/golden/isa/static_image_parent.json holds their figures
     from the commit before this feature (profiles/tools/isa_stats.py with RWARE_ISA_JSON, run on a worktree of that commit), as
     static_parent.json does for groups 0 and 3.  A guard, not the proof of the feature: it passes on that commit too."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc) or not shutil.which("c++filt"):
+    if not os.path.exists(isa_stats.HIPCC) or not shutil.which("c++filt"):
         pytest.skip("no hipcc / c++filt on this box")
     rec = json.load(open(os.path.join(ROOT, "tests", "golden", "isa", "static_image_parent.json")))
-    ver = "\n".join(l for l in subprocess.run([hipcc, "--version"], capture_output=True, text=True).stdout.splitlines() if "version" in l)
+    ver = isa_stats.hipcc_version()
     if ver != rec["hipcc"]:
         pytest.skip(f"the figures were recorded with another hipcc:\n{rec['hipcc']}\nthis box has:\n{ver}")
     assert rec["groups"] == [1]
-    csrc = os.path.join(ROOT, "robotic-warehouse_amd", "csrc")
-    out = tmp_path / "static_g1.s"
-    pr = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + csrc, "-mllvm", "-amdgpu-kernarg-preload-count=16",
-                         "-DRW_STATIC_GROUP=1", "--cuda-device-only", "-S", "-o", str(out), os.path.join(csrc, "rware_static.hip")],
-                        capture_output=True, timeout=900)
-    assert pr.returncode == 0, pr.stderr.decode()[-2000:]
-    got = {f"g1 {k}": v for k, v in _isa_of(out.read_text()).items()}
+    got = {f"g1 {k}": v for k, v in isa_stats.fingerprints(open(isa_stats.listings(str(tmp_path), [1])[1]).read()).items()}
     image = [k for k in got if k.rstrip(">").endswith(", 1")]     # (kObs == OBS_IMAGE, the last template argument)
     assert len(rec["kernels"]) >= 6 and image and set(got) == set(rec["kernels"])
     diff = {k: (rec["kernels"][k], got[k]) for k in got if got[k] != rec["kernels"][k]}

@@ -5,12 +5,10 @@ GPU — the generic kernel, the run-time exact-shape packed build and rw_unpack_
 The reference in every comparison is the float32 observation of the golden fixtures (recorded from the unmodified reference) or of
 the oracle; every comparison is exact (np.array_equal / torch.equal): unpacking is defined to reproduce RW_BUF_OBS bit for bit."""
 import ctypes as C
-import hashlib
+import importlib.util
 import json
 import os
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -24,6 +22,9 @@ import rware_amd
 from rware_amd import _capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "profiles", "tools", "isa_stats.py"))
+isa_stats = importlib.util.module_from_spec(_spec)      # the tool that recorded tests/golden/isa/*.json: its compile and its figures
+_spec.loader.exec_module(isa_stats)
 pytestmark = pytest.mark.timeout(1500)
 
 
@@ -304,47 +305,21 @@ def test_packed_runtime_builds_compile_without_a_device_and_get_their_own_cache_
 
 
 # ------------------------------------------------------------------------------------------------ CPU: the ahead-of-time ISA guard
-def _isa_of(listing):
-    """{instantiation: figures} per rw::rware_step_kernel in an assembly listing — profiles/tools/isa_stats.py's figures."""
-    lines = listing.splitlines()
-    starts = [i for i, l in enumerate(lines) if re.match(r"^_ZN2rw17rware_step_kernel.*:\s*(;.*)?$", l)]
-    out = {}
-    for a, b in zip(starts, starts[1:] + [len(lines)]):
-        body = lines[a:b]
-        name = subprocess.run(["c++filt", lines[a].split(":")[0]], capture_output=True, text=True).stdout.strip()
-        name = re.sub(r"^void rw::rware_step_kernel", "", name).split("(")[0]
-        ops = [l.split()[0] for l in body if re.match(r"^\s+[a-z_][a-z0-9_]*(\s|$)", l) and not l.strip().startswith((".", ";"))]
-
-        def meta(key):
-            return next((int(m.group(1)) for l in body for m in [re.match(rf"^; {key}: (\d+)", l)] if m), -1)
-        out[name] = {"inst": len(ops), "ophash": hashlib.sha1(" ".join(ops).encode()).hexdigest()[:10], "vgpr": meta("NumVgprs"),
-                     "sgpr": meta("TotalNumSgprs"), "lds": meta("LDSByteSize"), "scratch": meta("ScratchSize")}
-    return out
-
-
 def test_ahead_of_time_kernels_keep_the_parent_commits_isa(tmp_path):
     """The packed rows exist only behind RW_PACKED_BUILD (generic kernels, run-time builds): the ~100 ahead-of-time exact-shape
     kernels must come out instruction for instruction as before.  tests/golden/isa/static_parent.json holds, per rware_step_kernel
     instantiation of table groups 0 (the BASELINE shapes, the headline among them) and 3, the instruction count, a hash of the opcode
     sequence and the register / LDS / scratch figures of the commit before this feature (profiles/tools/isa_stats.py with
     RWARE_ISA_JSON, run on a worktree of that commit).  The guard, not the proof of the feature: it passes on that commit too."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc) or not shutil.which("c++filt"):
+    if not os.path.exists(isa_stats.HIPCC) or not shutil.which("c++filt"):
         pytest.skip("no hipcc / c++filt on this box")
     rec = json.load(open(os.path.join(ROOT, "tests", "golden", "isa", "static_parent.json")))
-    ver = "\n".join(l for l in subprocess.run([hipcc, "--version"], capture_output=True, text=True).stdout.splitlines() if "version" in l)
+    ver = isa_stats.hipcc_version()
     if ver != rec["hipcc"]:
         pytest.skip(f"the figures were recorded with another hipcc:\n{rec['hipcc']}\nthis box has:\n{ver}")
-    csrc = os.path.join(ROOT, "robotic-warehouse_amd", "csrc")
-    procs = [(g, subprocess.Popen(
-        [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + csrc, "-mllvm", "-amdgpu-kernarg-preload-count=16",
-         f"-DRW_STATIC_GROUP={g}", "--cuda-device-only", "-S", "-o", str(tmp_path / f"static_g{g}.s"), os.path.join(csrc, "rware_static.hip")],
-        stdout=subprocess.PIPE, stderr=subprocess.PIPE)) for g in rec["groups"]]
     got = {}
-    for g, pr in procs:
-        _, err = pr.communicate(timeout=900)
-        assert pr.returncode == 0, err.decode()[-2000:]
-        got.update({f"g{g} {k}": v for k, v in _isa_of((tmp_path / f"static_g{g}.s").read_text()).items()})
+    for g, path in isa_stats.listings(str(tmp_path), rec["groups"]).items():
+        got.update({f"g{g} {k}": v for k, v in isa_stats.fingerprints(open(path).read()).items()})
     assert len(rec["kernels"]) > 20 and set(got) == set(rec["kernels"])
     diff = {k: (rec["kernels"][k], got[k]) for k in got if got[k] != rec["kernels"][k]}
     assert not diff, f"{len(diff)} ahead-of-time kernels changed: {list(diff.items())[:3]}"
